@@ -33,8 +33,18 @@ Launch contract: under torch.distributed.run (WORLD_SIZE set) this process is on
 --master-port <free> bench.py <same arguments>` as a child process before anything
 touches the GPU (the parent imports neither torch nor librt_hip) and returns its exit code.
 
+A plain run sets up, warms up, times the K steps and prints the result line.  --full adds
+what takes runs of its own: the reference CPU baseline (cpu_baseline, speedup_vs_cpu), one
+frame alone (frame_latency_ms), one frame with the segment counters on (msegments_per_s,
+segments_per_primary) and the fp64 kernel on the same workload (f64_side).
+
+--dump-outputs DIR: rank 0 writes what the last timed step produced as DIR/<name>.npy
+(float32 / float64): frame_u8 (the 8-bit frame in host memory, H x W x 3) and sums (the
+accumulated per-pixel sums the frame was quantised from, as the render left them); an array
+too large for its share of the 64 MB budget is written as a fixed, seeded sample of its rows.
+
 Usage: python bench.py [--gpus N] [--steps K] [--warmup W] [--scene random|mesh|mixed]
-                       [--precision f32|f64]
+                       [--precision f32|f64] [--full] [--dump-outputs DIR]
 """
 from __future__ import annotations
 
@@ -65,6 +75,11 @@ def parse(argv: list[str] | None = None):
     p.add_argument("--steps", type=int, default=5)
     p.add_argument("--warmup", type=int, default=2)
     p.add_argument("--scene", choices=["random", "mesh", "mixed"], default="random")
+    p.add_argument("--full", action="store_true",
+                   help="also run what the headline does not need: the reference CPU baseline, one frame alone "
+                        "(frame_latency_ms), one frame with segment counters, the fp64 side line")
+    p.add_argument("--dump-outputs", default=None, metavar="DIR",
+                   help="rank 0 writes the last timed step's outputs to DIR/<name>.npy (float32/float64, <= 64 MB)")
     p.add_argument("--precision", choices=["f32", "f64"], default="f32",
                    help="f64: the reference-precision kernel (bit-exact to the reference goldens)")
     p.add_argument("--mesh-level", type=int, default=7, help="procedural blob: 20*4^level triangles")
@@ -79,11 +94,11 @@ def parse(argv: list[str] | None = None):
     p.add_argument("--depth", type=int, default=50)
     p.add_argument("--seed", type=lambda s: int(s, 0), default=0x5EED)
     p.add_argument("--cpu-workers", type=int, default=None,
-                   help="reference CPU processes (default: every CPU this process may use)")
+                   help="--full: reference CPU processes (default: every CPU this process may use)")
     p.add_argument("--cpu-spp", type=int, default=8)
-    p.add_argument("--no-cpu-baseline", action="store_true")
+    p.add_argument("--no-cpu-baseline", action="store_true", help="--full without the reference CPU baseline")
     p.add_argument("--f64-side-frames", type=int, default=2,
-                   help="--precision f32 at N = 1: warm fp64-kernel frames timed after the headline loop "
+                   help="--full, --precision f32 at N = 1: warm fp64-kernel frames timed after the headline loop "
                         "(the line's f64_side; 0 = off)")
     p.add_argument("--gather", choices=["capi", "torch", "host"], default="capi",
                    help="capi: RCCL ncclGather through the C ABI (rt_gather_shards; default); torch: "
@@ -273,6 +288,32 @@ def f64_side_line(W: int, H: int, spp: int, frame_ms: list[float], kernel: str) 
                                        "loop (not part of value / ms_per_step)"}
 
 
+DUMP_BUDGET_BYTES = 60 * 1000 * 1000   # --dump-outputs: all arrays together stay under 64 MB
+DUMP_SAMPLE_SEED = 0x5EED
+
+
+def dump_outputs(out_dir: str, arrays: dict) -> dict:
+    """Write each array as <out_dir>/<name>.npy in float32 (float64 stays float64).  Every
+    array has an equal share of DUMP_BUDGET_BYTES; one that is larger is cut to a seeded
+    sample of its rows (axis 0), the same rows for the same shape in every run and build.
+    Returns {name: {"shape", "dtype", "rows_sampled_of"}} for the result line."""
+    d = Path(out_dir)
+    d.mkdir(parents=True, exist_ok=True)
+    share = DUMP_BUDGET_BYTES // max(1, len(arrays))
+    desc = {}
+    for name, a in arrays.items():
+        a = np.ascontiguousarray(a, dtype=np.float64 if a.dtype == np.float64 else np.float32)
+        rows = a.shape[0]
+        row_bytes = max(1, a.nbytes // max(1, rows))
+        keep = min(rows, share // row_bytes)
+        if keep < rows:
+            idx = np.sort(np.random.default_rng(DUMP_SAMPLE_SEED).choice(rows, size=keep, replace=False))
+            a = a[idx]
+        np.save(d / f"{name}.npy", a)
+        desc[name] = {"shape": list(a.shape), "dtype": str(a.dtype), "rows_sampled_of": rows if keep < rows else None}
+    return desc
+
+
 def _free_port() -> int:
     import socket
     with socket.socket(socket.AF_INET, socket.SOCK_STREAM) as s:
@@ -331,9 +372,9 @@ def main(argv: list[str] | None = None) -> int:
     capi = args.gather == "capi" and use_dist
     coll_dev = dev if args.gather == "torch" else "cpu"   # the default group's tensors (nccl: device)
 
-    # CPU baseline first (rank 0, N=1 only) so it never overlaps the timed GPU region
+    # --full: CPU baseline first (rank 0, N=1 only) so it never overlaps the timed GPU region
     cpu = None
-    if rank == 0 and world_size == 1 and not args.no_cpu_baseline and args.scene == "random" and \
+    if args.full and rank == 0 and world_size == 1 and not args.no_cpu_baseline and args.scene == "random" and \
             args.precision == "f32":
         cpu = cpu_baseline(args.cpu_workers, args.cpu_spp, args.width)
 
@@ -418,6 +459,7 @@ def main(argv: list[str] | None = None) -> int:
     kernel_events = []
     gather_events = []
     nframe = [0]
+    last_src = [None]   # rank 0: the sums buffer the last frame was quantised from
 
     def step(timed: bool, count_segments: bool = False):
         if timed:
@@ -451,6 +493,7 @@ def main(argv: list[str] | None = None) -> int:
             b = nframe[0] % nbuf
             if copy_done[b] is not None:
                 stream.wait_event(copy_done[b])   # frame buffer b is free once its last copy is done
+            last_src[0] = src
             r.finish_u8(src.data_ptr(), W, H, world_size, spp, rgb8[b].data_ptr(), sp)
             ready = torch.cuda.Event()
             ready.record(stream)
@@ -498,32 +541,42 @@ def main(argv: list[str] | None = None) -> int:
     # a slow or throttled GPU shows in the fraction, not only in kernel_ms_per_rank
     slowest = int(np.argmax(per_rank_ms))
 
-    # latency of one frame on its own (render -> host bytes, nothing overlapped)
-    torch.cuda.synchronize(dev)
-    if use_dist:
-        dist.barrier()
-    t1 = time.perf_counter()
-    step(False)
-    torch.cuda.synchronize(dev)
-    frame_latency_ms = (time.perf_counter() - t1) * 1e3
-    last_frame = (nframe[0] - 1) % nbuf
+    # --dump-outputs: what the last timed step left (before any further frame reuses the buffers)
+    dumped = None
+    if rank == 0 and args.dump_outputs:
+        dumped = dump_outputs(args.dump_outputs, {
+            "frame_u8": host8[last_frame].numpy().reshape(H, W, 3),
+            "sums": last_src[0].cpu().numpy().reshape(-1, 3)})
 
-    # segment statistics (msegments_per_s): one more untimed frame with the per-pixel
-    # segment counters on -- instrumentation atomics the timed frames do not carry
-    step(False, count_segments=True)
-    torch.cuda.synchronize(dev)
-    segs_shard = int(seg_buf.to(torch.int64).sum().item())
+    frame_latency_ms, segs_total = None, None
+    if args.full:
+        # latency of one frame on its own (render -> host bytes, nothing overlapped)
+        torch.cuda.synchronize(dev)
+        if use_dist:
+            dist.barrier()
+        t1 = time.perf_counter()
+        step(False)
+        torch.cuda.synchronize(dev)
+        frame_latency_ms = (time.perf_counter() - t1) * 1e3
+        last_frame = (nframe[0] - 1) % nbuf
+
+        # segment statistics (msegments_per_s): one more untimed frame with the per-pixel
+        # segment counters on -- instrumentation atomics the timed frames do not carry
+        step(False, count_segments=True)
+        torch.cuda.synchronize(dev)
+        segs_total = int(seg_buf.to(torch.int64).sum().item())
+    rays_check = rays_shard
     if use_dist:
-        t = torch.tensor([segs_shard, rays_shard], dtype=torch.int64, device=coll_dev)
+        t = torch.tensor([segs_total or 0, rays_shard], dtype=torch.int64, device=coll_dev)
         dist.all_reduce(t)
-        segs_total, rays_check = map(int, t.tolist())
-    else:
-        segs_total, rays_check = segs_shard, rays_shard
+        rays_check = int(t[1].item())
+        if args.full:
+            segs_total = int(t[0].item())
 
     # the reference-precision kernel on the same workload, after everything the headline
     # measures (one GPU, fp32 headline, random spheres): f64_side
     f64_side = None
-    if not f64 and world_size == 1 and args.f64_side_frames > 0 and args.scene == "random":
+    if args.full and not f64 and world_size == 1 and args.f64_side_frames > 0 and args.scene == "random":
         r64 = N.Renderer(device_index, args.seed, N.RT_PREC_F64)
         try:
             r64.upload_scene(S, M, None)
@@ -599,10 +652,11 @@ def main(argv: list[str] | None = None) -> int:
                        **({"tuning_overrides": args.tune} if args.tune else {})},
             "roofline": sphere_roofline(f64, bool(tun.traversal & N.RT_TRAV_COH), kernel_ms, slowest, rays_launch,
                                         traffic, traffic_src),
+            "full": args.full,
             "cpu_baseline": cpu,
-            "msegments_per_s": round(segs_total * args.steps / elapsed / 1e6, 2),
-            "segments_per_primary": round(segs_total / total_rays, 4),
-            "frame_latency_ms": round(frame_latency_ms, 3),
+            **({"msegments_per_s": round(segs_total * args.steps / elapsed / 1e6, 2),
+                "segments_per_primary": round(segs_total / total_rays, 4),
+                "frame_latency_ms": round(frame_latency_ms, 3)} if args.full else {}),
             **({"kernel_ms_per_rank": {"min": round(min(per_rank_ms), 3), "max": round(max(per_rank_ms), 3),
                                        "argmax": int(np.argmax(per_rank_ms)),
                                        "all": [round(x, 3) for x in per_rank_ms]},
@@ -639,6 +693,8 @@ def main(argv: list[str] | None = None) -> int:
             out["note"] = "host-staged gather (test mode): not a reportable number"
         if gather_note:
             out["gather_note"] = gather_note
+        if dumped:
+            out["dumped_outputs"] = dumped
         if args.dump:
             np.save(args.dump, host8[last_frame].numpy().reshape(H, W, 3))
         print(json.dumps(out), flush=True)

@@ -12,6 +12,7 @@ Fixtures
   image_ref.json           sha256 + spot pixels of /root/reference/image.ppm (decoded
                            from its UTF-16LE/CRLF form to the LF ASCII the binary prints)
   image_ref_p6.ppm.gz      the same image as binary P6 (for statistical comparisons)
+  image_ref_utf16.ppm.gz   the image file byte for byte as committed there (UTF-16LE, CRLF)
   pixelmatch.json          tests/tests.cpp PixelMatch: ray_color of the centre ray on the
                            ground-only scene + the first random_double() values
   scene_random.txt         the 485 spheres main.cpp builds (center, center_vec, radius,
@@ -99,6 +100,9 @@ def main() -> int:
     with open(HERE / "image_ref_p6.ppm.gz", "wb") as raw_f:
         with gzip.GzipFile(fileobj=raw_f, mode="wb", compresslevel=9, mtime=0) as f:
             f.write(f"P6\n{W} {H}\n255\n".encode() + px.tobytes())
+    with open(HERE / "image_ref_utf16.ppm.gz", "wb") as raw_f:
+        with gzip.GzipFile(fileobj=raw_f, mode="wb", compresslevel=9, mtime=0) as f:
+            f.write(raw)
 
     # -- PixelMatch + first draws --------------------------------------------------
     pm = run(["pixelmatch"]).split()

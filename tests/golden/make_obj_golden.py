@@ -7,6 +7,7 @@ Run here (where /root/reference exists):  python tests/golden/make_obj_golden.py
 """
 from __future__ import annotations
 
+import json
 import subprocess
 import sys
 from pathlib import Path
@@ -84,6 +85,28 @@ def main() -> None:
         txt = subprocess.run([str(dump), str(obj)], check=True, capture_output=True, text=True).stdout
         (OUT / f"{name}.tinyobj.txt").write_text(txt)
         print(name, txt.splitlines()[0], [l for l in txt.splitlines() if l.startswith("T")][0])
+    # the random polygon soups of tests/test_mesh.py (input and dump), so that the comparison
+    # also runs where obj_dump cannot be built
+    sys.path.insert(0, str(ROOT / "tests"))
+    from test_mesh import SOUP_SEEDS, _random_polygon_obj
+    soup = OUT.parent / "obj_soup"
+    soup.mkdir(exist_ok=True)
+    for seed in SOUP_SEEDS:
+        obj = soup / f"soup{seed}.obj"
+        obj.write_bytes(_random_polygon_obj(np.random.default_rng(seed), obj).encode())
+        txt = subprocess.run([str(dump), str(obj)], check=True, capture_output=True, text=True).stdout
+        (soup / f"soup{seed}.tinyobj.txt").write_text(txt)
+    # the malformed corpus: tinyobjloader's exit status per file, and its dump where it loads
+    corpus = OUT.parent / "obj_malformed"
+    recorded = OUT.parent / "obj_malformed_tinyobj"
+    recorded.mkdir(exist_ok=True)
+    status = {}
+    for obj in sorted(corpus.glob("*.obj")):
+        r = subprocess.run([str(dump), str(obj)], capture_output=True, text=True)
+        status[obj.name] = r.returncode
+        if r.returncode == 0:
+            (recorded / f"{obj.stem}.tinyobj.txt").write_text(r.stdout)
+    (recorded / "status.json").write_text(json.dumps(status, indent=1, sort_keys=True) + "\n")
 
 
 if __name__ == "__main__":

@@ -95,6 +95,30 @@ def test_f64_side_line_layout():
     assert bench.parse([]).f64_side_frames == 2 and bench.parse(["--f64-side-frames", "0"]).f64_side_frames == 0
 
 
+def test_dump_outputs_keeps_to_its_budget(tmp_path, monkeypatch):
+    """--dump-outputs: float32 (float64 stays) .npy files; an array over its share of the
+    budget becomes the same seeded sample of its rows in every run."""
+    import numpy as np
+
+    import bench
+    assert bench.DUMP_BUDGET_BYTES <= 64 * 1000 * 1000
+    a = bench.parse(["--dump-outputs", "d"])
+    assert a.dump_outputs == "d" and a.full is False and bench.parse(["--full"]).full is True
+    monkeypatch.setattr(bench, "DUMP_BUDGET_BYTES", 2 * 1200)
+    small = np.arange(60, dtype=np.uint8).reshape(4, 5, 3)
+    big = np.arange(900, dtype=np.float64).reshape(300, 3)
+    d1 = bench.dump_outputs(str(tmp_path / "a"), {"small": small, "big": big})
+    bench.dump_outputs(str(tmp_path / "b"), {"small": small, "big": big})
+    s, b = np.load(tmp_path / "a" / "small.npy"), np.load(tmp_path / "a" / "big.npy")
+    assert s.dtype == np.float32 and np.array_equal(s, small)
+    assert b.dtype == np.float64 and b.shape == (50, 3) and b.nbytes <= 1200
+    assert d1["small"]["rows_sampled_of"] is None and d1["big"] == {"shape": [50, 3], "dtype": "float64",
+                                                                    "rows_sampled_of": 300}
+    rows = (b[:, 0] / 3).astype(int)
+    assert (np.diff(rows) > 0).all() and np.array_equal(b, big[rows])      # whole rows, in order
+    assert np.array_equal(b, np.load(tmp_path / "b" / "big.npy"))
+
+
 def test_pmc_key_separates_shard_launches():
     """A full-frame PMC profile must not price an N-way shard launch: the
     workload key carries the shard count for N > 1, so roofline.traffic stays null there

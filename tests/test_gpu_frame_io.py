@@ -152,6 +152,35 @@ def test_bench_capi_rccl_path_one_rank(tmp_path):
     assert "gather_note" in out
 
 
+FULL_ONLY = {"frame_latency_ms", "msegments_per_s", "segments_per_primary", "f64_side"}
+
+
+def test_bench_plain_run_dumps_its_outputs(tmp_path):
+    """A plain run carries the headline fields and nothing that takes a run of its own;
+    --dump-outputs writes the last timed step's frame (equal to --dump's bytes) and sums."""
+    out = _bench(["--steps", "2", "--dump-outputs", str(tmp_path / "o")], tmp_path / "plain.npy")
+    line = json.loads(out.strip().splitlines()[-1])
+    assert line["steps"] == 2 and line["full"] is False and line["ms_per_step"] > 0
+    assert line["unit"] == "Mrays/s" and line["higher_is_better"] is True and line["dtype"] == "f32"
+    # value and ms_per_step say the same thing (both rounded to 3 decimals)
+    rel = 0.0006 / line["ms_per_step"] + 1e-6
+    assert abs(line["value"] - 264 * 148 * 3 / (line["ms_per_step"] * 1e-3) / 1e6) <= rel * line["value"] + 1e-3
+    assert not (FULL_ONLY & set(line)) and line["cpu_baseline"] is None
+    frame, sums = np.load(tmp_path / "o" / "frame_u8.npy"), np.load(tmp_path / "o" / "sums.npy")
+    assert sorted(p.name for p in (tmp_path / "o").iterdir()) == ["frame_u8.npy", "sums.npy"]
+    assert frame.dtype == np.float32 and frame.shape == (148, 264, 3)
+    assert np.array_equal(frame, np.load(tmp_path / "plain.npy").astype(np.float32))
+    assert sums.dtype == np.float32 and sums.shape[1] == 3 and len(sums) >= 148 * 264 and np.isfinite(sums).all()
+    assert line["dumped_outputs"]["frame_u8"] == {"shape": [148, 264, 3], "dtype": "float32", "rows_sampled_of": None}
+
+
+def test_bench_full_adds_the_side_measurements(tmp_path):
+    out = _bench(["--full", "--f64-side-frames", "1"], tmp_path / "full.npy")
+    line = json.loads(out.strip().splitlines()[-1])
+    assert line["full"] is True and FULL_ONLY <= set(line)
+    assert line["frame_latency_ms"] > 0 and line["segments_per_primary"] > 1 and line["f64_side"]["frames"] == 1
+
+
 def test_bench_self_launches_ranks(tmp_path):
     """`python bench.py --gpus 2` with no launcher (the way the driver runs BENCH) starts
     torch.distributed.run itself; two ranks (sharing this box's one GPU through the

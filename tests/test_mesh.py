@@ -80,9 +80,17 @@ def _random_polygon_obj(rng, path):
     return "\n".join(l + ("\r" if rng.uniform() < 0.3 else "") for l in lines) + "\n"
 
 
-@pytest.mark.skipif(not OBJ_DUMP.exists(), reason="oracle/_ref/obj_dump not built (needs /root/reference)")
-@pytest.mark.parametrize("seed", range(6))
+SOUP_SEEDS = range(6)
+GOLDEN_SOUP = O.GOLDEN / "obj_soup"   # tests/golden/make_obj_golden.py: each seed's soup and its tinyobjloader dump
+
+
+@pytest.mark.parametrize("seed", SOUP_SEEDS)
 def test_obj_load_matches_tinyobjloader_live(tmp_path, seed):
+    """The recorded soup of this seed against its recorded tinyobjloader dump, everywhere;
+    where oracle/_ref/obj_dump was built, also a soup made now against a dump made now."""
+    assert_same_parse(GOLDEN_SOUP / f"soup{seed}.obj", (GOLDEN_SOUP / f"soup{seed}.tinyobj.txt").read_text())
+    if not OBJ_DUMP.exists():
+        return
     rng = np.random.default_rng(seed)
     p = tmp_path / "soup.obj"
     p.write_text(_random_polygon_obj(rng, p))

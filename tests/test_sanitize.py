@@ -36,6 +36,7 @@ ROOT = Path(__file__).resolve().parents[1]
 CORPUS = ROOT / "tests" / "golden" / "obj_malformed"
 EXPECTED = json.loads((CORPUS / "expected.json").read_text()) if (CORPUS / "expected.json").exists() else {}
 OBJ_DUMP = O.ORACLE_DIR / "_ref" / "obj_dump"
+RECORDED = ROOT / "tests" / "golden" / "obj_malformed_tinyobj"
 LOG = ROOT / "raytracingproject_amd" / "build" / "san" / "sanitize.log"   # copied to profiles/ per round
 
 
@@ -137,18 +138,31 @@ def test_corpus_through_shipped_library():
         assert np.isfinite(V).all() and (F >= 0).all() and (F < max(nv, 1)).all()
 
 
-@pytest.mark.skipif(not OBJ_DUMP.exists(), reason="oracle/_ref/obj_dump not built (needs /root/reference)")
+def _tinyobj_recorded(name):
+    """obj_dump's exit status and output for a corpus file as tests/golden/make_obj_golden.py
+    recorded them (the output only where it loaded the file)."""
+    rc = json.loads((RECORDED / "status.json").read_text())[name]
+    return rc, (RECORDED / f"{Path(name).stem}.tinyobj.txt").read_text() if rc == 0 else ""
+
+
+def _tinyobj_live(name):
+    r = subprocess.run([str(OBJ_DUMP), str(CORPUS / name)], capture_output=True, text=True)
+    return r.returncode, r.stdout
+
+
 def test_corpus_against_tinyobjloader():
     """Where expected.json says "same", tinyobjloader (the reference's vendored copy, built
     unmodified into oracle/_ref/obj_dump) reads the file identically; the documented
-    divergences are checked to be what they say."""
+    divergences are checked to be what they say.  Checked against obj_dump's recorded
+    results everywhere, and against obj_dump itself where it was built."""
     from test_mesh import assert_same_parse
-    for name, (st, *_, how) in EXPECTED.items():
-        r = subprocess.run([str(OBJ_DUMP), str(CORPUS / name)], capture_output=True, text=True)
-        if how == "same":
-            assert r.returncode == 0, name
-            assert_same_parse(CORPUS / name, r.stdout)
-        elif how == "fails" or how.startswith("fails on"):
-            assert r.returncode != 0, name
-        else:   # tinyobjloader accepts what rt_obj_load refuses
-            assert r.returncode == 0 and st != N.RT_OK, name
+    for dump in [_tinyobj_recorded] + ([_tinyobj_live] if OBJ_DUMP.exists() else []):
+        for name, (st, *_, how) in EXPECTED.items():
+            rc, out = dump(name)
+            if how == "same":
+                assert rc == 0, name
+                assert_same_parse(CORPUS / name, out)
+            elif how == "fails" or how.startswith("fails on"):
+                assert rc != 0, name
+            else:   # tinyobjloader accepts what rt_obj_load refuses
+                assert rc == 0 and st != N.RT_OK, name

@@ -27,7 +27,7 @@ for s in $STEPS; do
     smoke) step smoke 400 python -c "import __graft_entry__ as g; g.smoke()" ;;
     tests) step tests 900 python -u -m pytest tests -m gpu -q -rA --timeout 300 --timeout-method thread ;;
     quick) step quick 600 python -u -m pytest tests/test_gpu_parity.py tests/test_mesh.py -m gpu -x -q -rA --timeout 300 --timeout-method thread -k "tuning or variants or coherent or golden or exact" ;;
-    bench) step bench 600 python bench.py ;;
+    bench) step bench 600 python bench.py --full ;;
     prof)  step prof 600 rocprofv3 --kernel-trace --stats -d "$OUT/prof" -o bench --output-format csv -- python3 bench.py --steps 3 --warmup 1 --no-cpu-baseline ;;
     prof2) step prof2 600 rocprofv3 --kernel-trace --stats -d "$OUT/prof2" -o target --output-format csv -- python3 tools/profile_target.py --frames 3 ;;
     pmc)   T="python3 tools/profile_target.py --frames 2 --meta $OUT/meta_c3.json"
@@ -39,11 +39,11 @@ for s in $STEPS; do
            step sq2 600 rocprofv3 --pmc SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_WAIT_INST_LDS SQ_LDS_BANK_CONFLICT SQ_LDS_IDX_ACTIVE SQ_THREAD_CYCLES_VALU SQ_ACTIVE_INST_ANY GRBM_GUI_ACTIVE -d "$OUT/sq2" -o pmc --output-format csv -- python3 tools/profile_target.py --frames 1
            step sq_sum 60 python3 tools/pmc_traffic.py "$OUT/sq.json" "$OUT/sq1" "$OUT/sq2" "$OUT/sq3" ;;
     mtests) step mtests 900 python -m pytest tests/test_mesh.py -m gpu -q -rA -s ;;
-    mbench) step mbench 600 python bench.py --scene mesh --no-cpu-baseline
-            step mbench_mixed 900 python bench.py --scene mixed --steps 3 --warmup 1
-            step mbench_gpubuild 600 python bench.py --scene mesh --no-cpu-baseline --mesh-builder gpu ;;
-    f64bench) step f64bench 600 python bench.py --precision f64 --width 1280 --spp 64 --steps 3 --warmup 1 --no-cpu-baseline
-              step f64bench_c3 600 python bench.py --precision f64 --steps 3 --warmup 1 --no-cpu-baseline
+    mbench) step mbench 600 python bench.py --full --scene mesh --no-cpu-baseline
+            step mbench_mixed 900 python bench.py --full --scene mixed --steps 3 --warmup 1
+            step mbench_gpubuild 600 python bench.py --full --scene mesh --no-cpu-baseline --mesh-builder gpu ;;
+    f64bench) step f64bench 600 python bench.py --full --precision f64 --width 1280 --spp 64 --steps 3 --warmup 1 --no-cpu-baseline
+              step f64bench_c3 600 python bench.py --full --precision f64 --steps 3 --warmup 1 --no-cpu-baseline
               step f64prof 600 rocprofv3 --kernel-trace --stats -d "$OUT/f64prof" -o f64 --output-format csv -- python3 tools/profile_target.py --precision f64 --frames 3 ;;
     # mesh configs at their bench sizes: kernel trace, then FETCH / WRITE passes filed under
     # the launch's PMC keys (profile_target --meta), for C4 (mesh 1080p x 128) and C5 (mixed 4K x 1024)
@@ -339,7 +339,7 @@ for s in $STEPS; do
     c5park) for i in 1 2; do
               step c5park_$i 900 python tools/variant_probe.py --scene mixed --width 3840 --spp 1024 --frames 2 --variants "mesh_lds_stack=1;coh_refill=40;coh_refill=56;mesh_item_balance=10.0;mesh_item_balance=40.0;item_samples=16;mesh_block=512"
             done
-            step mbench_mixed 900 python bench.py --scene mixed --steps 3 --warmup 1 ;;
+            step mbench_mixed 900 python bench.py --full --scene mixed --steps 3 --warmup 1 ;;
     # r06: frames in flight on the GPU (two render streams) against one stream, per N's shard
     pipe) step pipe_c3 600 python tools/pipeline_probe.py --ns 1,2,4,8 --frames 8 --reps 3
           step pipe_c4 600 python tools/pipeline_probe.py --scene mesh --spp 128 --ns 1,8 --frames 8 --reps 3
