@@ -443,7 +443,9 @@ int rt_render_diag(rt_ctx* ctx, const rt_camera* cam, int samples_per_pixel, int
  * flushed straight to HBM (their item was no longer the wave's current one, or a value
  * outside [0, 1]), 26 item flushes (per pixel); mesh scenes add 27-30: 27 mesh-BVH node
  * wave iterations, 28 their active lanes, 29 triangle-test wave iterations, 30 their active
- * lanes. */
+ * lanes.  31: grid walks suspended (the sphere-only kernel over the flat grid walk, see
+ * RT_GRID_SUSPEND in INTEGRATION.md; 0 for every other kernel); a resumed walk counts no new
+ * world.hit call in slot 10, though its trace counts in slots 0 and 1. */
 enum { RT_DIAG_SLOTS = 32 };
 int rt_render_diag_ex(rt_ctx* ctx, const rt_camera* cam, int samples_per_pixel, int max_depth, uint64_t* counters,
                       int n);

@@ -439,7 +439,9 @@ class Renderer:
                  # coherent kernel: framebuffer traffic
                  "samples_in_item", "samples_direct", "item_flushes",
                  # mesh scenes: mesh BVH node visits and triangle tests (iterations, active lanes)
-                 "mnode_it", "mnode_act", "mtri_it", "mtri_act", "x31"]
+                 "mnode_it", "mnode_act", "mtri_it", "mtri_act",
+                 # resumable flat grid walks (RT_GRID_SUSPEND): suspended walks
+                 "grid_suspensions"]
         return {n: int(c[k]) for k, n in enumerate(names)}
 
     def trace_rays(self, rays_dev: int, n: int, hits_dev: int, stream: int | None = None) -> None:

@@ -145,6 +145,25 @@ def build_sanitize(verbose: bool = False) -> Path:
     return SAN_EXE
 
 
+RESUME_EXE = OBJ / "san" / "grid_resume_driver"
+
+
+def build_grid_resume(verbose: bool = False) -> Path:
+    """tests/cpp/grid_resume_driver.cpp (the flat grid walk with suspension, restated for the
+    CPU; run by tests/test_grid_resume.py) with csrc/rt_bvh.cpp, which builds its grids, under
+    the same sanitizers as build_sanitize.  No GPU code."""
+    RESUME_EXE.parent.mkdir(parents=True, exist_ok=True)
+    srcs = [ROOT / "tests" / "cpp" / "grid_resume_driver.cpp", CSRC / "rt_bvh.cpp"]
+    deps = srcs + [CSRC / "rt_bvh.h", CSRC / "rt_scene.h", ROOT / "include" / "rt_hip.h", Path(__file__)]
+    if _stale(RESUME_EXE, deps):
+        cmd = ["g++", "-std=c++17", *SAN_FLAGS, "-ffp-contract=off", f"-I{ROOT / 'include'}", *map(str, srcs), "-o",
+               str(RESUME_EXE), "-lm"]
+        if verbose:
+            print(" ".join(cmd), flush=True)
+        subprocess.run(cmd, check=True)
+    return RESUME_EXE
+
+
 def build_oracle(verbose: bool = False) -> None:
     """Compile the C restatement (test infrastructure) and, where /root/reference is
     present, the reference driver into oracle/_ref (test infrastructure: oracle/_ref/

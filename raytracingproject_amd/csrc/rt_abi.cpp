@@ -496,12 +496,36 @@ const char* rt_error_string(int code) {
     }
 }
 
+// RT_GRID_SUSPEND: "LANES,ITERS" (resumable flat grid walks, rt_device.h closest_hit SUSP),
+// "0" for none; unset or empty keeps the defaults.  A tuning that is no rt_tuning field: the
+// frame does not depend on it, and the ABI stays what it is.
+static bool parse_grid_suspend(const char* s, int& lanes, int& iters) {
+    if (!s || !*s) return true;
+    int l = 0, i = 0, n = 0;
+    if (sscanf(s, "%d,%d%n", &l, &i, &n) == 2 && !s[n] && l >= 1 && l <= 64 && i >= 1 && i <= 65535) {
+        lanes = l;
+        iters = i;
+        return true;
+    }
+    if (s[0] == '0' && !s[1]) {
+        lanes = 0;
+        iters = 0x7fffffff;   // (one block: the countdown never ends a walk)
+        return true;
+    }
+    return false;
+}
+
 rt_ctx* rt_create(int device, uint64_t seed, int precision) {
     if (precision != RT_PREC_F32 && precision != RT_PREC_F64) return nullptr;
     int n = 0;
     if (hipGetDeviceCount(&n) != hipSuccess || device < 0 || device >= n) return nullptr;
     if (hipSetDevice(device) != hipSuccess) return nullptr;
     rt_ctx* c = new rt_ctx();
+    if (!parse_grid_suspend(getenv("RT_GRID_SUSPEND"), c->gsus_lanes, c->gsus_iters)) {
+        fprintf(stderr, "rt_create: RT_GRID_SUSPEND must be \"0\" or \"LANES,ITERS\" (1..64, 1..65535)\n");
+        delete c;
+        return nullptr;
+    }
     c->device = device;
     c->seed = seed;
     c->precision = precision;
@@ -1243,8 +1267,10 @@ int rt_render_range(rt_ctx* c, const rt_camera* cam, int sample_begin, int spp, 
         // the grid walk reads cells and records by LDS byte address, counting from 0: the
         // kernel's dynamic LDS must start there, i.e. the kernel has no static LDS (rt_device.h)
         const bool f64 = c->precision == RT_PREC_F64;
+        // (the instrumented copy is another kernel: rt_render_diag launches it instead)
         const int s = f64 ? render_f64_static_lds(c->n_mnodes > 0, f64_kernel_of(c))
-                          : render_f32_static_lds(plan.block, plan.wpe, plan.trav, c->n_mnodes > 0);
+                      : c->diag_buf ? render_f32_diag_static_lds(block_of(c), plan_of(c).wpe, trav_of(c), c->n_mnodes > 0)
+                                    : render_f32_static_lds(plan.block, plan.wpe, plan.trav, c->n_mnodes > 0);
         if (s != 0) return fail(c, RT_ERR_HIP, "grid render kernel with %d B of static LDS (needs none)", s);
     }
     apply_grid(c, plan.trav, P);
@@ -1281,6 +1307,8 @@ int rt_render_range(rt_ctx* c, const rt_camera* cam, int sample_begin, int spp, 
         P.accp = slot->accp;
         P.diag = c->diag_buf;
         P.coh_refill = c->tuning.coh_refill;
+        P.gsus_lanes = c->gsus_lanes;
+        P.gsus_iters = c->gsus_iters;
         // persistent lanes: no more workgroups than the device keeps resident
         if (!slot->queue) HIPCHK(c, hipMalloc((void**)&slot->queue, QUEUE_CTRL_BYTES));
         P.queue = slot->queue;

@@ -50,6 +50,9 @@ struct rt_ctx {
     double reach_lo[3] = {0, 0, 0}, reach_hi[3] = {0, 0, 0};
     std::vector<std::array<double, 4>> reach_big;
     bool grid_blocked = false;  // the current launch's rays could start beyond grid_hdr.far_o: the tree
+    // r07: resumable flat grid walks (RenderParams::gsus_lanes / gsus_iters), from the
+    // environment's RT_GRID_SUSPEND at rt_create
+    int gsus_lanes = GSUS_DEFAULT_LANES, gsus_iters = GSUS_DEFAULT_ITERS;
     int* d_remap = nullptr;     // rt_trace_rays: kernel id slot -> input index (spheres | big | triangles)
     Node4* d_mnodes = nullptr;  // mesh BVH (4-wide) + triangles (HBM-resident)
     void* d_tris = nullptr;

@@ -202,7 +202,13 @@ struct RenderParams {
     // t < 2^51 (the quotient lies >= 0.5 / tiles_x from an integer, its error is <=
     // (t + 0.5) 2^-52 / tiles_x), and three VALU instead of a 32-bit integer division's ~20
     double tiles_x_inv, tiles_x_inv_half;
+    // resumable flat grid walks (r07, closest_hit SUSP; the environment's RT_GRID_SUSPEND at
+    // rt_create): between blocks of gsus_iters iterations the lanes still walking suspend once
+    // they are at most gsus_lanes (0: never)
+    int gsus_lanes, gsus_iters;
 };
+// (the defaults: profiles/r07/cpu/grid_resume_bound_r07.txt, then measured: DESIGN.md §5 r07)
+constexpr int GSUS_DEFAULT_LANES = 16, GSUS_DEFAULT_ITERS = 8;
 constexpr size_t QUEUE_CTRL_BYTES = 4096;   // RenderParams::queue: 8 heads x 128 B (+ room)
 constexpr int FIX_SHIFT = 28;          // accum: 64-bit integers in units of 2^-28
 constexpr int FIX_SAMPLE_SHIFT = 19;   // each sample's radiance rounded to a multiple of 2^-19
@@ -620,9 +626,17 @@ typedef __attribute__((address_space(3))) const uint32_t lds_cu32;
 typedef __attribute__((address_space(3))) const float4 lds_cf4;
 // Keep a loaded word live without an instruction (forces the full-width LDS read).
 __device__ __forceinline__ void keep_live(uint32_t v) { asm volatile("" ::"v"(v)); }
-template <class R, bool EXACT, bool DIAG = false, int TRAV = 0, bool MESH = false>
+// SUSP (r07, render_coherent's bounce trace over the flat grid walk only): the walk may stop
+// early and be resumed by a later call.  *resume < 0 on entry: a fresh ray; >= 0: the
+// distance a suspended walk of this ray stopped at, with its closest hit so far in *part.
+// On return *resume >= 0 says that this walk was suspended there (the returned hit is then
+// the closest so far), < 0 that it is complete.  sus_lanes / sus_iters: RenderParams.
+template <class R, bool EXACT, bool DIAG = false, int TRAV = 0, bool MESH = false, bool SUSP = false>
 __device__ __forceinline__ Hit<R> closest_hit(const SceneView<R>& sc, const Ray<R>& ray, uint16_t* stack, int stride,
-                                              int self_id, DiagCounters* dg = nullptr) {
+                                              int self_id, DiagCounters* dg = nullptr, float* resume = nullptr,
+                                              const Hit<R>* part = nullptr, int sus_lanes = 0, int sus_iters = 0) {
+    static_assert(!SUSP || (!EXACT && !MESH && (TRAV & TRAV_GRID) != 0 && (TRAV & TRAV_GFLAT) != 0),
+                  "resumable walks: the fp32 sphere-only flat grid walk");
     constexpr R TMIN = (R)0.001;
     Hit<R> h;
     h.id = -1;
@@ -631,9 +645,25 @@ __device__ __forceinline__ Hit<R> closest_hit(const SceneView<R>& sc, const Ray<
     const V3<R> o = ray.o, d = ray.d;
     const R a = len2(d);
     const R inv_a = rcp(a);
+    // a resumed lane starts from its partial hit (h.t of a walk without a hit is +inf, as here)
+    // and skips the big spheres and the front list, which its first pass tested
+    // (*resume is taken here, so that every way out of this call without a new suspension --
+    // a resumed ray clipped to nothing among them -- leaves it negative: complete)
+    [[maybe_unused]] bool resumed = false;
+    [[maybe_unused]] float t_from = -1.f;
+    if constexpr (SUSP) {
+        t_from = *resume;
+        *resume = -1.f;
+        resumed = t_from >= 0.f;
+        if (resumed) {
+            h.id = part->id;
+            tmax = part->t;
+        }
+    }
 
     // big spheres (rt_scene.h BIG_RADIUS)
-    if (EXACT) {
+    if (SUSP && resumed) {
+    } else if (EXACT) {
         // reference arithmetic, fp64 (sphere.h:30-57)
         const V3<double> od = cvt<double>(o), dd = cvt<double>(d);
         double tmaxd = __builtin_huge_val();
@@ -702,7 +732,7 @@ __device__ __forceinline__ Hit<R> closest_hit(const SceneView<R>& sc, const Ray<
     auto test_one = [&](int k, R tlim, R& tk) -> bool { return test_rec(sc.sph + k, k == self_id, tlim, tk); };
     // front list (rt_tuning.front_spheres): the largest spheres, tested by every lane
     // before the tree; the closest hit is the same in any test order
-    for (int k = 0; k < sc.n_front; ++k) {
+    for (int k = 0; k < (SUSP && resumed ? 0 : sc.n_front); ++k) {
         R t;
         if (test_one(k, tmax, t)) {
             tmax = t;
@@ -775,6 +805,16 @@ __device__ __forceinline__ Hit<R> closest_hit(const SceneView<R>& sc, const Ray<
                 const float t0z = fmaf(bz.x, inv.z, -oi.z), t1z = fmaf(bz.y, inv.z, -oi.z);
                 tn = fmaxf(fmaxf(fminf(t0x, t1x), fminf(t0y, t1y)), fmaxf(fminf(t0z, t1z), (float)TMIN));
                 tf = fminf(fminf(fmaxf(t0x, t1x), fmaxf(t0y, t1y)), fminf(fmaxf(t0z, t1z), (float)tmax));
+                // SUSP: a resumed walk re-enters where it stopped, through this same set-up (a
+                // fresh ray's *resume is negative).  Its entry cell is that of the point at the
+                // resume distance, which lies on the entry plane of the cell the walk stopped in
+                // to within the rounding of a plane distance and of that point, 2^-22 (|o| + ext):
+                // the cell found is the stop cell or the one before it on the ray.  Every sphere
+                // the ray reaches beyond that point is listed in the cell it is reached in -- the
+                // listed boxes are padded beyond this rounding, the argument that already covers
+                // a fresh ray's entry cell -- and spheres tested twice change nothing: the sphere
+                // test is exact per sphere and only a strictly closer root replaces the hit.
+                if constexpr (SUSP) tn = fmaxf(tn, t_from);
                 // the entry cell, and per axis the distance to its exit plane and the step
                 // between planes (never along a zero direction component)
                 auto axis = [&](int a, float oa, float da, float iv, float oia, float& n, float& dt) {
@@ -817,49 +857,125 @@ __device__ __forceinline__ Hit<R> closest_hit(const SceneView<R>& sc, const Ray<
                 // the grid or passes the front / big spheres' hit), then tests one sphere of
                 // its cell -- a single loop, so that lanes stepping through empty cells and
                 // lanes testing spheres share every iteration
-                for (;;) {
-                    if (cur >= end) {
-                        if (DIAG) DiagCounters::count(dg->inner_it, dg->inner_act), ++dg->steps;
-                        // (a step out of the grid happens only within the rounding of its exit,
-                        // the ray's last step: past the first or last layer it reads an empty
-                        // pad cell, past a row's or slab's end the neighbouring row's cell --
-                        // tests the exact sphere test settles, never a different hit -- and the
-                        // next exit ends the loop)
-                        if constexpr (FLAT) {
-                            // (a compare and a select: fminf's NaN rules cost two more VALU)
-                            const bool bx = nx <= nz;
-                            const float te = bx ? nx : nz;
-                            if (!(te < (float)tmax && te < tf)) break;
-                            ca += bx ? sx4 : sz4;
-                            nx = bx ? nx + dtx : nx;
-                            nz = bx ? nz : nz + dtz;
-                        } else {
-                            const float te = fminf(fminf(nx, ny), nz);
-                            if (!(te < (float)tmax && te < tf)) break;
-                            const bool bx = nx == te, by = !bx && ny == te, bz = !bx && !by;
-                            ci += bx ? stx : (by ? sty : stz);
-                            nx = bx ? nx + dtx : nx;
-                            ny = by ? ny + dty : ny;
-                            nz = bz ? nz + dtz : nz;
+                if constexpr (!SUSP) {
+                    for (;;) {
+                        if (cur >= end) {
+                            if (DIAG) DiagCounters::count(dg->inner_it, dg->inner_act), ++dg->steps;
+                            // (a step out of the grid happens only within the rounding of its exit,
+                            // the ray's last step: past the first or last layer it reads an empty
+                            // pad cell, past a row's or slab's end the neighbouring row's cell --
+                            // tests the exact sphere test settles, never a different hit -- and the
+                            // next exit ends the loop)
+                            if constexpr (FLAT) {
+                                // (a compare and a select: fminf's NaN rules cost two more VALU)
+                                const bool bx = nx <= nz;
+                                const float te = bx ? nx : nz;
+                                if (!(te < (float)tmax && te < tf)) break;
+                                ca += bx ? sx4 : sz4;
+                                nx = bx ? nx + dtx : nx;
+                                nz = bx ? nz : nz + dtz;
+                            } else {
+                                const float te = fminf(fminf(nx, ny), nz);
+                                if (!(te < (float)tmax && te < tf)) break;
+                                const bool bx = nx == te, by = !bx && ny == te, bz = !bx && !by;
+                                ci += bx ? stx : (by ? sty : stz);
+                                nx = bx ? nx + dtx : nx;
+                                ny = by ? ny + dty : ny;
+                                nz = bz ? nz + dtz : nz;
+                            }
+                            w = FLAT ? *(const lds_cu32*)(uintptr_t)ca : cells[ci];
+                            cur = w & GRID_POS_MASK;
+                            end = w >> GRID_POS_BITS;
                         }
-                        w = FLAT ? *(const lds_cu32*)(uintptr_t)ca : cells[ci];
-                        cur = w & GRID_POS_MASK;
-                        end = w >> GRID_POS_BITS;
+                        if (cur < end) {
+                            if (DIAG) DiagCounters::count(dg->leaf_it, dg->leaf_act), ++dg->steps;
+                            const uint32_t off = *(const lds_cu32*)(uintptr_t)cur;   // (cur: an LDS byte address)
+                            cur += 4u;
+                            R t;
+                            // the record straight from its LDS byte address: the grid buffer is the
+                            // first thing in the kernel's dynamic LDS, which starts at address 0 (the
+                            // render kernels have no static LDS: rt_abi.cpp checks it per launch),
+                            // saving the add of a base the compiler only learns to be 0 after ISel
+                            const Sph* rec = (const Sph*)(const float4*)(const lds_cf4*)(uintptr_t)off;
+                            if (test_rec(rec, off == self_off, tmax, t)) {
+                                tmax = t;
+                                hit_off = off;
+                            }
+                        }
                     }
-                    if (cur < end) {
-                        if (DIAG) DiagCounters::count(dg->leaf_it, dg->leaf_act), ++dg->steps;
-                        const uint32_t off = *(const lds_cu32*)(uintptr_t)cur;   // (cur: an LDS byte address)
-                        cur += 4u;
-                        R t;
-                        // the record straight from its LDS byte address: the grid buffer is the
-                        // first thing in the kernel's dynamic LDS, which starts at address 0 (the
-                        // render kernels have no static LDS: rt_abi.cpp checks it per launch),
-                        // saving the add of a base the compiler only learns to be 0 after ISel
-                        const Sph* rec = (const Sph*)(const float4*)(const lds_cf4*)(uintptr_t)off;
-                        if (test_rec(rec, off == self_off, tmax, t)) {
-                            tmax = t;
-                            hit_off = off;
+                } else {
+                    // Resumable walk (r07).  A wave iterates until its longest ray is done, at
+                    // 0.16 / 0.20 lane utilisation; here the walk runs in blocks of sus_iters
+                    // iterations -- the body above plus a wave-uniform countdown -- and only
+                    // between blocks the wave counts the lanes still walking (the lanes that
+                    // have not left the loop).  Once they are at most sus_lanes, and fewer than
+                    // entered this trace (somebody has a hit to shade), they suspend: the caller
+                    // keeps their closest hit so far and *resume, shades the others, and traces
+                    // the suspended lanes again together with the next scattered rays.
+                    // The resume distance is the entry distance of the lane's current cell, from
+                    // what the walk carries: the later of its two entry planes (an axis the ray
+                    // does not move along has none), never below TMIN.  The cell's list is
+                    // tested again from its start after the resume.
+                    // Termination: a resumed lane suspends again only if its new resume distance
+                    // exceeds the one it resumed from by 15/16 of the smaller plane step m =
+                    // min(dtx, dtz) -- the advance per step of the reach proof above; a lane that
+                    // cannot show that walks on to its end in this pass, the plain walk.  Resume
+                    // distances lie in [tn, tf) of the first pass, an interval no longer than
+                    // res[a] steps of the axis a with the smaller step (the slab clip), so a ray
+                    // suspends at most 2 + 16/15 res[a] times -- no more than res[0] + res[2] + 2
+                    // unless one axis has over 15 times the other's cells -- and each pass is a
+                    // plain walk of at most res[0] + res[2] + 2 steps.
+                    const int entered = __builtin_amdgcn_readfirstlane((int)__popcll(__ballot(1)));
+                    int block = sus_iters;
+                    for (;;) {   // (a second turn only for lanes that may not suspend)
+                        int left = __builtin_amdgcn_readfirstlane(block);
+                        for (;;) {   // the flat walk's iteration, as above
+                            if (cur >= end) {
+                                if (DIAG) DiagCounters::count(dg->inner_it, dg->inner_act), ++dg->steps;
+                                const bool bx = nx <= nz;
+                                const float te = bx ? nx : nz;
+                                if (!(te < (float)tmax && te < tf)) break;
+                                ca += bx ? sx4 : sz4;
+                                nx = bx ? nx + dtx : nx;
+                                nz = bx ? nz : nz + dtz;
+                                w = *(const lds_cu32*)(uintptr_t)ca;
+                                cur = w & GRID_POS_MASK;
+                                end = w >> GRID_POS_BITS;
+                            }
+                            if (cur < end) {
+                                if (DIAG) DiagCounters::count(dg->leaf_it, dg->leaf_act), ++dg->steps;
+                                const uint32_t off = *(const lds_cu32*)(uintptr_t)cur;
+                                cur += 4u;
+                                R t;
+                                const Sph* rec = (const Sph*)(const float4*)(const lds_cf4*)(uintptr_t)off;
+                                if (test_rec(rec, off == self_off, tmax, t)) {
+                                    tmax = t;
+                                    hit_off = off;
+                                }
+                            }
+                            // the countdown: one scalar subtract, compare and branch (an SGPR by
+                            // constraint: the compiler otherwise carries it in a VGPR)
+                            if constexpr (DIAG)
+                                left = __builtin_amdgcn_readfirstlane(left) - 1;
+                            else
+                                asm volatile("s_sub_u32 %0, %0, 1" : "+s"(left) : : "scc");
+                            if (left == 0) {
+                                const int walking = (int)__popcll(__ballot(1));
+                                if (walking <= sus_lanes && walking < entered) break;   // (the whole wave)
+                                left = __builtin_amdgcn_readfirstlane(block);
+                            }
                         }
+                        // which lanes left at a block's end: those whose walk is not over (a lane
+                        // that would have ended in its next iteration counts as ended)
+                        const float te = nx <= nz ? nx : nz;
+                        if (!(cur < end || (te < (float)tmax && te < tf))) break;
+                        const float ex = nx < INF ? nx - dtx : -INF, ez = nz < INF ? nz - dtz : -INF;
+                        const float tc = fmaxf(fmaxf(ex, ez), (float)TMIN);
+                        if (!resumed || tc >= fmaf(0.9375f, fminf(dtx, dtz), t_from)) {
+                            *resume = tc;
+                            break;
+                        }
+                        block = 0x7fffffff;   // no progress to show: the plain walk to its end
                     }
                 }
             }

@@ -20,6 +20,7 @@ int render_f64_vgprs(bool mesh, int kernel);   // kernel: rt_tuning.f64_kernel (
 // static LDS bytes of an instantiated render kernel (-1: not instantiated / query failed); the
 // sphere grid's walk addresses its dynamic LDS from 0, so a grid kernel must have none
 int render_f32_static_lds(int block, int waves_per_eu, int trav, bool mesh);
+int render_f32_diag_static_lds(int block, int waves_per_eu, int trav, bool mesh);   // the instrumented copy's
 int render_f64_static_lds(bool mesh, int kernel);
 int render_f64_block(int kernel);              // its threads per workgroup (-1: no such kernel)
 int render_f64_trav(int kernel);               // its traversal flags (TRAV_*)

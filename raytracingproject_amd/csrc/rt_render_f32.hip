@@ -169,6 +169,26 @@ int render_f32_static_lds(int block, int waves_per_eu, int trav, bool mesh) {
     return -1;
 }
 
+int render_f32_diag_static_lds(int block, int waves_per_eu, int trav, bool mesh) {
+    hipFuncAttributes a;
+#define RT_DSLDS(B, W, T, M)                                                                                 \
+    if (block == B && waves_per_eu == W && trav == T)                                                        \
+        return hipFuncGetAttributes(&a, (const void*)render_kernel<float, false, B, W, true, T, M>) == hipSuccess \
+                   ? (int)a.sharedSizeBytes                                                                  \
+                   : -1;
+#define RT_DSLDS_S(B, W, T) RT_DSLDS(B, W, T, false)
+#define RT_DSLDS_M(B, W, T) RT_DSLDS(B, W, T, true)
+    if (mesh) {
+        RT_DIAG_MESH_VARIANTS(RT_DSLDS_M)
+    } else {
+        RT_DIAG_VARIANTS(RT_DSLDS_S)
+    }
+#undef RT_DSLDS
+#undef RT_DSLDS_S
+#undef RT_DSLDS_M
+    return -1;
+}
+
 hipError_t launch_render_f32(const RenderParams& P, size_t lds_bytes, hipStream_t stream, int block,
                              int waves_per_eu, int trav) {
 #define RT_CASE(B, W, T) \

@@ -587,6 +587,13 @@ __device__ __forceinline__ void render_coherent(const RenderParams& P0, const Sc
 
     // this lane's path
     bool live = false, ready = false, fin = false;   // holds a path; holds a hit to shade; no work left
+    // r07: the bounce trace of the sphere-only flat grid walk may suspend a lane's walk
+    // (closest_hit SUSP).  Such a lane stays live and not ready: it shades nothing, pops
+    // nothing, does not count as idle, keeps its ray, self, pix, rng, elig and scatter count,
+    // and the next trace resumes its walk from tres with the closest hit so far in h.
+    constexpr bool SUSP = !EXACT && !MESH && (TR & TRAV_GRID) != 0 && (TR & TRAV_GFLAT) != 0;
+    [[maybe_unused]] float tres = -1.f;              // >= 0: the suspended walk's resume distance
+    [[maybe_unused]] unsigned long long n_susp = 0;  // DIAG: suspensions
     uint32_t pix = 0;
     uint32_t psid = 0;   // EXACT: the path's sample - sample_begin
     V3<R> thr = mk((R)1, (R)1, (R)1);
@@ -749,9 +756,19 @@ __device__ __forceinline__ void render_coherent(const RenderParams& P0, const Sc
                     if (dry) ++n_drain;
                 }
             }
-            if (DIAG) ++n_seg;
-            h = closest_hit<R, EXACT, DIAG, TR, MESH>(sc, ray, stack, BLOCK, EXACT ? NO_SELF : self, &dg);
-            ready = true;
+            if constexpr (SUSP) {
+                // (a resumed pass is not a new segment; the partial hit travels in h)
+                if (DIAG && tres < 0.f) ++n_seg;
+                const Hit<R> part = h;
+                h = closest_hit<R, EXACT, DIAG, TR, MESH, true>(sc, ray, stack, BLOCK, self, &dg, &tres, &part,
+                                                                P.gsus_lanes, P.gsus_iters);
+                ready = tres < 0.f;
+                if (DIAG && !ready) ++n_susp;
+            } else {
+                if (DIAG) ++n_seg;
+                h = closest_hit<R, EXACT, DIAG, TR, MESH>(sc, ray, stack, BLOCK, EXACT ? NO_SELF : self, &dg);
+                ready = true;
+            }
         }
         if (DIAG && lane == 0) cyc_trav += __builtin_amdgcn_s_memtime() - ttr;
     }
@@ -769,6 +786,7 @@ __device__ __forceinline__ void render_coherent(const RenderParams& P0, const Sc
         if (n_in_item) atomicAdd(P.diag + 24, n_in_item);
         if (n_direct) atomicAdd(P.diag + 25, n_direct);
         if (n_item_flush) atomicAdd(P.diag + 26, n_item_flush);
+        if (n_susp) atomicAdd(P.diag + 31, n_susp);
         if constexpr (MESH) {   // mesh BVH loops (batches and bounces together)
             const unsigned long long mv[4] = {dg.mnode_it + dgb.mnode_it, dg.mnode_act + dgb.mnode_act,
                                               dg.mtri_it + dgb.mtri_it, dg.mtri_act + dgb.mtri_act};

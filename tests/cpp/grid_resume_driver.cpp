@@ -1,0 +1,294 @@
+// grid_resume_driver.cpp -- the flat grid walk with suspension (rt_device.h closest_hit, SUSP),
+// restated for the CPU and built with -fsanitize=address,undefined (build.py
+// build_grid_resume, run by tests/test_grid_resume.py).  No GPU code.
+//
+//   grid_resume_driver SPHERES.f32 RAYS
+//
+// SPHERES.f32: n x 7 floats (centre, radius, centre motion) -- the spheres a grid lists.  For
+// grids over them (build_sphere_grid, two densities, 32 time slabs, one cell tall in y) and
+// RAYS rays of each family (random, grazing, axis-aligned, from points on cell planes, from
+// as far as the grid's far_o, at every time-slab edge), the walk is run unsuspended and with a
+// suspension attempted after every ITERS in {1, 2, 3, 8} iterations (LANES = 64: a lone ray
+// always counts as the last lane walking).  For every ray: the same hit (id and t bits) as the
+// unsuspended walk, which finds the brute-force closest hit; resume distances growing by the
+// stated margin; at most res_x + res_z + 2 suspensions; a bounded number of iterations.
+#include <cmath>
+#include <cstdint>
+#include <cstdio>
+#include <cstdlib>
+#include <cstring>
+#include <random>
+#include <string>
+#include <vector>
+
+#include "../../raytracingproject_amd/csrc/rt_bvh.h"
+#include "../../raytracingproject_amd/csrc/rt_scene.h"
+
+using namespace rtx;
+
+static long long checks_failed = 0;
+static void check(bool ok, const char* what) {
+    if (!ok && ++checks_failed <= 20) std::printf("CHECK FAILED: %s\n", what);
+}
+
+// the exact sphere test both walks and brute force share: closest root beyond 0.001
+static double sphere_t(const SphereF& q, const double o[3], const double d[3], double tm) {
+    double oc[3], a = 0, h = 0, cc = 0;
+    for (int x = 0; x < 3; ++x) {
+        oc[x] = (double)q.c[x] + tm * (double)q.cv[x] - o[x];
+        a += d[x] * d[x];
+        h += d[x] * oc[x];
+        cc += oc[x] * oc[x];
+    }
+    cc -= (double)q.r * (double)q.r;
+    const double disc = h * h - a * cc;
+    if (disc < 0) return INFINITY;
+    const double sq = std::sqrt(disc);
+    double t = (h - sq) / a;
+    if (!(t > 0.001)) t = (h + sq) / a;
+    return t > 0.001 ? t : INFINITY;
+}
+
+struct Grid {
+    GridHdr hd;
+    std::vector<unsigned char> buf;
+    const uint32_t* cells;
+    uint32_t pad, lb;
+    std::vector<uint32_t> ids;   // list entry -> sphere
+    const float* sb;
+    float slo(int k, int x) const { return sb[((size_t)x * (hd.n_slab + 1) + k) * 2]; }
+    float shi(int k, int x) const { return sb[((size_t)x * (hd.n_slab + 1) + k) * 2 + 1]; }
+    uint32_t first_of(uint32_t w) const { return w == 0 ? 0u : (w & GRID_POS_MASK) / 4 - lb; }
+    uint32_t end_of(uint32_t w) const { return w == 0 ? 0u : (w >> GRID_POS_BITS) / 4 - lb; }
+};
+
+struct Ray {
+    double o[3], d[3], tm;
+};
+struct Result {
+    double t = INFINITY;
+    int id = -1;
+    int suspensions = 0;
+    long long iterations = 0;
+};
+
+// One pass of the kernel's flat walk from resume distance t_from (< 0: a fresh ray) with the
+// closest hit so far in r; iters: iterations per block (0: never suspend).  Returns the new
+// resume distance, or -1 when the walk is complete.
+static float walk_pass(const Grid& G, const std::vector<SphereF>& sf, const Ray& ray, float t_from, int iters,
+                       Result& r) {
+    const GridHdr& hd = G.hd;
+    const float INF = INFINITY;
+    const bool resumed = t_from >= 0.f;
+    const float of[3] = {(float)ray.o[0], (float)ray.o[1], (float)ray.o[2]};
+    const float df[3] = {(float)ray.d[0], (float)ray.d[1], (float)ray.d[2]};
+    float inv[3], oi[3], t0[3], t1[3];
+    const float tmf = (float)ray.tm;
+    const int sk = tmf >= 0.f && tmf <= 1.f ? std::min((int)(tmf * hd.slab_k), hd.n_slab - 1) : hd.n_slab;
+    for (int x = 0; x < 3; ++x) {
+        inv[x] = 1.0f / (df[x] + std::copysign(0x1p-100f, df[x]));
+        oi[x] = of[x] * inv[x];
+        t0[x] = std::fmaf(G.slo(sk, x), inv[x], -oi[x]);
+        t1[x] = std::fmaf(G.shi(sk, x), inv[x], -oi[x]);
+    }
+    float tn = std::fmax(std::fmax(std::fmin(t0[0], t1[0]), std::fmin(t0[1], t1[1])),
+                         std::fmax(std::fmin(t0[2], t1[2]), 0.001f));
+    const float tf = std::fmin(std::fmin(std::fmax(t0[0], t1[0]), std::fmax(t0[1], t1[1])),
+                               std::fmin(std::fmax(t0[2], t1[2]), (float)r.t));
+    tn = std::fmax(tn, t_from);
+    if (!(tn <= tf)) return -1.f;
+    int i[3];
+    float nx[3], dt[3];
+    for (int x = 0; x < 3; x += 2) {
+        int c = (int)((std::fmaf(tn, df[x], of[x]) - hd.lo[x]) * hd.inv_cs[x]);
+        c = c < 0 ? 0 : (c >= hd.res[x] ? hd.res[x] - 1 : c);
+        const float plane = std::fmaf((float)(df[x] > 0 ? c + 1 : c), hd.cs[x], hd.lo[x]);
+        nx[x] = df[x] != 0 ? std::fmaf(plane, inv[x], -oi[x]) : INF;
+        dt[x] = hd.cs[x] * std::fabs(inv[x]);
+        i[x] = c;
+    }
+    int ci = i[2] * hd.res[0] + i[0];
+    const int st[3] = {df[0] > 0 ? 1 : -1, 0, df[2] > 0 ? hd.res[0] : -hd.res[0]};
+    uint32_t w = G.cells[ci];
+    uint32_t cur = G.first_of(w), end = G.end_of(w);
+    const int max_steps = hd.res[0] + hd.res[2] + 2;
+    int steps = 0;
+    int block = iters > 0 ? iters : 0x7fffffff;
+    for (;;) {
+        int left = block;
+        for (;;) {
+            ++r.iterations;
+            if (cur >= end) {
+                const bool bx = nx[0] <= nx[2];
+                const float te = bx ? nx[0] : nx[2];
+                if (!(te < (float)r.t && te < tf)) break;
+                ci += bx ? st[0] : st[2];
+                nx[0] = bx ? nx[0] + dt[0] : nx[0];
+                nx[2] = bx ? nx[2] : nx[2] + dt[2];
+                check(++steps <= max_steps, "a pass takes at most res_x + res_z + 2 steps");
+                const bool inside = ci >= -(int)G.pad && ci < (int)(hd.n_cells + G.pad);
+                check(inside, "a step out of the grid stays within the pad layers");
+                if (!inside || steps > max_steps) return -1.f;
+                w = G.cells[ci];
+                cur = G.first_of(w);
+                end = G.end_of(w);
+            }
+            if (cur < end) {
+                const uint32_t id = G.ids[cur];
+                ++cur;
+                const double t = sphere_t(sf[id], ray.o, ray.d, ray.tm);
+                if (t < r.t) r.t = t, r.id = (int)id;
+            }
+            if (--left == 0) break;   // a block's end: LANES = 64, so the lane asks to suspend
+        }
+        const float te = nx[0] <= nx[2] ? nx[0] : nx[2];
+        if (!(cur < end || (te < (float)r.t && te < tf))) return -1.f;   // the walk is over
+        const float ex = nx[0] < INF ? nx[0] - dt[0] : -INF, ez = nx[2] < INF ? nx[2] - dt[2] : -INF;
+        const float tc = std::fmax(std::fmax(ex, ez), 0.001f);
+        if (!resumed || tc >= std::fmaf(0.9375f, std::fmin(dt[0], dt[2]), t_from)) {
+            if (resumed) {
+                check(tc > t_from, "resume distances strictly increase");
+                check(tc - t_from >= 0.9374f * std::fmin(dt[0], dt[2]), "... by 15/16 of the smaller plane step");
+            }
+            return tc;
+        }
+        block = 0x7fffffff;   // no progress to show: the plain walk to its end
+    }
+}
+
+static Result trace(const Grid& G, const std::vector<SphereF>& sf, const Ray& ray, int iters) {
+    Result r;
+    float t_from = -1.f;
+    const int max_susp = G.hd.res[0] + G.hd.res[2] + 2;
+    for (;;) {
+        t_from = walk_pass(G, sf, ray, t_from, iters, r);
+        if (t_from < 0.f) break;
+        if (++r.suspensions > max_susp) {
+            check(false, "at most res_x + res_z + 2 suspensions");
+            break;
+        }
+    }
+    return r;
+}
+
+static bool make_grid(const std::vector<SphereF>& sf, double density, int slabs, Grid& G) {
+    if (!build_sphere_grid(sf.data(), 0, (int)sf.size(), density, slabs, (int)sizeof(SphereF), G.hd, G.buf)) return false;
+    G.pad = (uint32_t)G.hd.res[0] * G.hd.res[1];
+    G.cells = (const uint32_t*)G.buf.data() + G.pad;
+    G.lb = G.hd.n_cells + 2 * G.pad;
+    const uint32_t* offs = (const uint32_t*)G.buf.data() + G.lb;
+    const size_t nent = (G.hd.slab_off - (size_t)G.lb * 4) / 4;
+    for (size_t k = 0; k < nent; ++k) G.ids.push_back((uint32_t)((offs[k] - G.buf.size()) / sizeof(SphereF)));
+    G.sb = (const float*)(G.buf.data() + G.hd.slab_off);
+    return true;
+}
+
+int main(int argc, char** argv) {
+    if (argc < 3) return 2;
+    std::vector<SphereF> sf;
+    {
+        FILE* f = std::fopen(argv[1], "rb");
+        if (!f) return 2;
+        float v[7];
+        while (std::fread(v, sizeof(float), 7, f) == 7) {
+            SphereF s{};
+            for (int x = 0; x < 3; ++x) s.c[x] = v[x], s.cv[x] = v[4 + x];
+            s.r = v[3];
+            sf.push_back(s);
+        }
+        std::fclose(f);
+    }
+    const int rays = std::atoi(argv[2]);
+    std::mt19937 g(0x5EEDu);
+    std::uniform_real_distribution<double> u(0.0, 1.0);
+    long long traced = 0, suspensions = 0, missed = 0;
+    int grids = 0, most = 0;
+    for (double density : {2.0, 8.0}) {
+        Grid G;
+        if (!make_grid(sf, density, 32, G)) continue;
+        const GridHdr& hd = G.hd;
+        check(hd.res[1] == 1, "the field's grid is one cell tall in y");
+        if (hd.res[1] != 1) continue;
+        ++grids;
+        const int slabs = hd.n_slab;
+        double span[3];
+        for (int x = 0; x < 3; ++x) span[x] = (double)hd.hi[x] - hd.lo[x];
+        const int families = 6;
+        for (int r = 0; r < rays * families; ++r) {
+            Ray ray;
+            ray.tm = u(g);
+            for (int x = 0; x < 3; ++x) {
+                ray.o[x] = hd.lo[x] - 0.2 * span[x] + 1.4 * span[x] * u(g);
+                ray.d[x] = u(g) * 2 - 1;
+            }
+            switch (r % families) {
+            case 0: break;   // random rays through and around the box
+            case 1: {        // grazing rays from inside the field: elevation 0.01 .. 0.12
+                const double az = 6.283185307179586 * u(g), el = (0.01 + 0.11 * u(g)) * (r % 2 ? 1 : -1);
+                ray.o[1] = hd.lo[1] + span[1] * u(g);
+                ray.d[0] = std::cos(az) * std::cos(el), ray.d[1] = std::sin(el), ray.d[2] = std::sin(az) * std::cos(el);
+                break;
+            }
+            case 2: {   // axis-aligned: along +-x or +-z, the other components exactly zero
+                const int a = (r / families) % 2 ? 0 : 2;
+                ray.d[0] = ray.d[1] = ray.d[2] = 0.0;
+                ray.d[a] = (r / families / 2) % 2 ? 1.0 : -1.0;
+                ray.o[1] = hd.lo[1] + span[1] * u(g);
+                break;
+            }
+            case 3: {   // from a point exactly on a cell plane of x, z or both
+                const int which = (r / families) % 3;
+                for (int x = 0; x < 3; x += 2)
+                    if (which == 2 || which == x / 2)
+                        ray.o[x] = std::fmaf((float)(int)(u(g) * (hd.res[x] + 1)), hd.cs[x], hd.lo[x]);
+                ray.o[1] = hd.lo[1] + span[1] * u(g);
+                break;
+            }
+            case 4: {   // aimed at the box from 10^-4 .. 1 of far_o away (origins beyond far_o are dropped below)
+                const double dist = (double)hd.far_o * std::pow(10.0, -4.0 * u(g)) * 0.99;
+                double len = 0, tgt[3];
+                for (int x = 0; x < 3; ++x) len += ray.d[x] * ray.d[x], tgt[x] = hd.lo[x] + span[x] * u(g);
+                len = std::sqrt(len);
+                for (int x = 0; x < 3; ++x) ray.o[x] = tgt[x] - ray.d[x] / len * dist;
+                break;
+            }
+            case 5: {   // every time-slab edge, either side of it, and the ends of the shutter
+                const int k = (r / families) % (slabs + 1);
+                ray.tm = std::nextafter((double)k / slabs, (r / families / (slabs + 1)) % 2 ? 2.0 : -1.0);
+                if (k == 0 && ray.tm < 0) ray.tm = 0.0;
+                if (k == slabs && ray.tm > 1) ray.tm = 1.0;
+                break;
+            }
+            }
+            const float om = std::fmax(std::fmax(std::fabs((float)ray.o[0]), std::fabs((float)ray.o[1])),
+                                       std::fabs((float)ray.o[2]));
+            if (!(om <= hd.far_o)) continue;   // (never walked by the product: rt_abi.cpp grid_reach_ok)
+            double best = INFINITY;
+            int best_id = -1;
+            for (size_t k = 0; k < sf.size(); ++k) {
+                const double t = sphere_t(sf[k], ray.o, ray.d, ray.tm);
+                if (t < best) best = t, best_id = (int)k;
+            }
+            const Result plain = trace(G, sf, ray, 0);
+            check(plain.suspensions == 0, "the unsuspended walk never suspends");
+            if (plain.id != best_id && !(best == plain.t)) ++missed;
+            const long long bound = (long long)(hd.res[0] + hd.res[2] + 3) * (hd.res[0] + hd.res[2] + 2 + (long long)G.ids.size());
+            for (int iters : {1, 2, 3, 8}) {
+                const Result s = trace(G, sf, ray, iters);
+                uint64_t a, b;
+                std::memcpy(&a, &s.t, 8);
+                std::memcpy(&b, &plain.t, 8);
+                check(s.id == plain.id && a == b, "the suspended walk finds the unsuspended walk's hit, id and t bits");
+                check(s.iterations <= bound, "total iterations bounded");
+                suspensions += s.suspensions;
+                most = std::max(most, s.suspensions);
+                ++traced;
+            }
+        }
+    }
+    check(missed == 0, "the walk reaches every brute-force closest hit");
+    check(grids == 2, "both grids built");
+    std::printf("resume grids %d traced %lld suspensions %lld most %d checks failed %lld\n", grids, traced, suspensions,
+                most, checks_failed);
+    return checks_failed ? 1 : 0;
+}

@@ -16,6 +16,17 @@ is clipped to the box of the spheres at its time's slab (rt_scene.h GridHdr), by
 long (near-horizontal) rays once enough of them wait, and its short ones otherwise, each trace
 round costing its slowest lane plus a shade pass of `shade` loop iterations: wave iterations
 per 64 traced rays against tracing every lane every round.
+
+--resume LANES,ITERS (r07; "sweep": LANES in 8, 16, 24, 32 x ITERS in 4, 8, 12, 16): resumable
+walks on the current walk (flat grid, 32 time slabs, the real lists) -- a wave traces in blocks
+of ITERS iterations and, between blocks, suspends the lanes still walking once they are at most
+LANES (and fewer than entered the trace); the others shade and take their next ray, and the
+suspended lanes walk on in the next trace.  Wave cost per 64 finished rays, in loop iterations:
+every trace round pays the set-up once (--setup-cost: the slab clip and the two axis() set-ups,
+56 VALU in the kernel's ISA against 61 per iteration), its iterations, and a shade round
+(--shade-cost: the shade share of a bounce round from the DIAG counters, in iterations); a
+resumed ray pays --resume-cost more iterations (the stop cell's list tested again from its
+start, and at most one cell entered again).
 """
 import argparse
 import math
@@ -214,8 +225,52 @@ def defer_bound(its, key, shades=(0, 4, 8, 12)):
               f"(tau {best[1]}, L {best[2]}) {best[0] / base - 1:+.1%}", flush=True)
 
 
+def resume_bound(its, settings, setup, shade, resume):
+    """A wave of 64 lanes over the stream of rays `its` (loop iterations each): rounds of
+    (set-up, blocks of iterations, shade); see the module text."""
+    n = len(its)
+
+    def sim(lanes_max, iters):
+        nxt, rem, cost, done, susp, rounds = 64, its[:64].astype(float), 0.0, 0, 0, 0
+        while nxt < n - 64:
+            entered, el = 64, 0
+            while True:
+                walking = int((rem > el).sum())
+                if walking == 0:
+                    break
+                if iters and el and el % iters == 0 and walking <= lanes_max and walking < entered:
+                    break
+                el += 1
+            cost += setup + el + shade
+            rounds += 1
+            fin = rem <= el
+            k = int(fin.sum())
+            susp += 64 - k
+            rem = np.where(fin, 0.0, rem - el + resume)
+            rem[fin] = its[nxt:nxt + k]
+            nxt += k
+            done += k
+        return cost / done * 64, susp / done, rounds / done * 64
+
+    base, _, _ = sim(64, 0)
+    print(f"set-up {setup}, shade {shade}, resume {resume} iterations; no suspension: {base:.2f} wave iterations "
+          f"per 64 rays")
+    out = {}
+    for ln, it in settings:
+        c, sp, rd = sim(ln, it)
+        out[(ln, it)] = c
+        print(f"LANES {ln:2d} ITERS {it:2d}: {c:6.2f} per 64 rays ({c / base - 1:+.1%}), {sp:.3f} suspensions per ray, "
+              f"{rd:.2f} rounds per 64 rays", flush=True)
+    best = min(out, key=out.get)
+    print(f"best: LANES {best[0]}, ITERS {best[1]} ({out[best] / base - 1:+.1%})")
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--resume", default=None, metavar="LANES,ITERS", help="resumable walks (round 7); 'sweep': the table")
+    ap.add_argument("--setup-cost", type=float, default=1.0)
+    ap.add_argument("--shade-cost", type=float, default=8.0)
+    ap.add_argument("--resume-cost", type=float, default=2.0)
     ap.add_argument("--paths", type=int, default=40000)
     ap.add_argument("--rays", type=int, default=20000)
     ap.add_argument("--regroup", action="store_true",
@@ -238,6 +293,16 @@ def main():
         return
     O, D, TH = paths(C, V, R, M, a.paths, rng)
     print(f"{len(O)} rays over {a.paths} paths")
+    if a.resume:
+        O, D, TH, TM = paths(C, V, R, M, a.paths, np.random.default_rng(1), times=True)
+        idx = np.random.default_rng(0).permutation(len(O))[:a.rays]
+        its = loop_iterations(C, V, R, O[idx], D[idx], TH[idx], (29, 1, 29), TM[idx], 32)
+        print(f"{len(idx)} scattered rays, {its.mean():.2f} loop iterations per ray, a wave's slowest of 64 "
+              f"{its[:len(its) // 64 * 64].reshape(-1, 64).max(1).mean():.2f}")
+        sets = ([(l, i) for l in (8, 16, 24, 32) for i in (4, 8, 12, 16)] if a.resume == "sweep"
+                else [tuple(int(x) for x in a.resume.split(","))])
+        resume_bound(its, sets, a.setup_cost, a.shade_cost, a.resume_cost)
+        return
     if a.defer:
         O, D, TH, TM = paths(C, V, R, M, a.paths, np.random.default_rng(1), times=True)
         idx = np.random.default_rng(0).permutation(len(O))[:a.rays]
