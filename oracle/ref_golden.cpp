@@ -167,6 +167,23 @@ static void build_scene(const std::string& name, hittable_list& world, CPUImpl::
     } else if (name == "ground") {
         // tests.cpp:26-29
         world.add(make_shared<sphere>(point3(0, -1000, 0), 1000, make_shared<lambertian>(color(0.5, 0.5, 0.5))));
+    } else if (name == "hollow") {
+        // negative radii (sphere.h:35 squares the radius, :52 divides the normal by it): the
+        // "four" scene with a shell inside its glass sphere and its metal sphere inside out, a
+        // moving hollow bubble, glass of ir 1/1.5, an inside-out lambertian and a metal whose
+        // fuzz material.h:33 clamps (scenes.hollow_glass() in the product's Python layer)
+        world.add(make_shared<sphere>(point3(0, -1000, 0), 1000, make_shared<lambertian>(color(0.5, 0.5, 0.5))));
+        auto glass = make_shared<dielectric>(1.5);
+        world.add(make_shared<sphere>(point3(0, 1, 0), 1.0, glass));
+        world.add(make_shared<sphere>(point3(0, 1, 0), -0.9, glass));
+        world.add(make_shared<sphere>(point3(-4, 1, 0), 1.0, make_shared<lambertian>(color(0.4, 0.2, 0.1))));
+        world.add(make_shared<sphere>(point3(4, 1, 0), -1.0, make_shared<metal>(color(0.7, 0.6, 0.5), 0.0)));
+        auto bubble = make_shared<dielectric>(1.5);
+        world.add(make_shared<sphere>(point3(2, 0.3, 2), point3(2, 0.6, 2), 0.3, bubble));
+        world.add(make_shared<sphere>(point3(2, 0.3, 2), point3(2, 0.6, 2), -0.25, bubble));
+        world.add(make_shared<sphere>(point3(-2, 0.4, 2), 0.4, make_shared<dielectric>(1.0 / 1.5)));
+        world.add(make_shared<sphere>(point3(5, 0.3, 1.5), -0.3, make_shared<lambertian>(color(0.2, 0.6, 0.3))));
+        world.add(make_shared<sphere>(point3(1, 0.35, 3), 0.35, make_shared<metal>(color(0.8, 0.8, 0.9), 3.0)));
     } else {
         fprintf(stderr, "unknown scene %s\n", name.c_str());
         exit(2);

@@ -164,6 +164,25 @@ def build_grid_resume(verbose: bool = False) -> Path:
     return RESUME_EXE
 
 
+BOXES_EXE = OBJ / "san" / "bvh_boxes_driver"
+
+
+def build_bvh_boxes(verbose: bool = False) -> Path:
+    """tests/cpp/bvh_boxes_driver.cpp (the sphere tree's boxes and the sphere grid over scenes
+    with negative radii; run by tests/test_bvh_boxes.py) with csrc/rt_bvh.cpp, which builds
+    both, under the same sanitizers as build_sanitize.  No GPU code."""
+    BOXES_EXE.parent.mkdir(parents=True, exist_ok=True)
+    srcs = [ROOT / "tests" / "cpp" / "bvh_boxes_driver.cpp", CSRC / "rt_bvh.cpp"]
+    deps = srcs + [CSRC / "rt_bvh.h", CSRC / "rt_scene.h", ROOT / "include" / "rt_hip.h", Path(__file__)]
+    if _stale(BOXES_EXE, deps):
+        cmd = ["g++", "-std=c++17", *SAN_FLAGS, "-ffp-contract=off", f"-I{ROOT / 'include'}", *map(str, srcs), "-o",
+               str(BOXES_EXE), "-lm"]
+        if verbose:
+            print(" ".join(cmd), flush=True)
+        subprocess.run(cmd, check=True)
+    return BOXES_EXE
+
+
 def build_oracle(verbose: bool = False) -> None:
     """Compile the C restatement (test infrastructure) and, where /root/reference is
     present, the reference driver into oracle/_ref (test infrastructure: oracle/_ref/

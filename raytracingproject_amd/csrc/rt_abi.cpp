@@ -859,10 +859,14 @@ int rt_upload_scene_ex(rt_ctx* c, const rt_sphere* s, int n, const rt_material* 
             len += nv[a] * nv[a];
         }
         len = std::sqrt(len);
+        // (a negative radius -- the reference's inside-out sphere: the near point is still
+        // centre + |r| na; n = (p0 - centre) / r and inv_r keep the radius' sign, so that
+        // f = q + r n and (p - c) / r = (p - p0) / r + n hold as they are in the kernels)
+        const double sgn = q.radius < 0 ? -1.0 : 1.0;
         for (int a = 0; a < 3; ++a) {
             const double na = len > 0 ? nv[a] / len : (a == 1 ? 1.0 : 0.0);
-            f.n[a] = (float)na;
-            f.p0[a] = (float)(q.center[a] + q.radius * na);
+            f.n[a] = (float)(sgn * na);
+            f.p0[a] = (float)(q.center[a] + std::fabs(q.radius) * na);
             f.cv[a] = q.moving ? (float)q.center_vec[a] : 0.0f;
         }
         f.r = (float)q.radius;

@@ -29,12 +29,15 @@ struct Box {
     }
 };
 
+// (|radius|: a negative radius is the reference's hollow sphere -- sphere.h's roots use
+// radius * radius and aabb.h orders the corners it is given)
 Box exact_box(const rt_sphere& s) {
     Box b;
+    const double r = std::fabs(s.radius);
     for (int a = 0; a < 3; ++a) {
         double c0 = s.center[a], c1 = s.center[a] + (s.moving ? s.center_vec[a] : 0.0);
-        b.lo[a] = std::min(c0, c1) - s.radius;
-        b.hi[a] = std::max(c0, c1) + s.radius;
+        b.lo[a] = std::min(c0, c1) - r;
+        b.hi[a] = std::max(c0, c1) + r;
     }
     return b;
 }

@@ -72,6 +72,28 @@ def ground_only() -> hittable_list:
     return world
 
 
+def hollow_glass() -> hittable_list:
+    """Negative radii, the hollow-glass construct: the hit roots use radius * radius
+    (sphere.h:35) and the normal (p - c) / radius flips (sphere.h:52).  Ten spheres: the
+    ground, main.cpp's three R = 1 spheres with a shell inside the glass one and the metal
+    one inside out, a moving hollow bubble, glass of ir 1/1.5, an inside-out lambertian and a
+    metal whose fuzz the constructor clamps.  Spheres 1, 2 and 5, 6 each share one material."""
+    world = hittable_list()
+    world.add(sphere((0, -1000, 0), 1000, lambertian((0.5, 0.5, 0.5))))
+    glass = dielectric(1.5)
+    world.add(sphere((0, 1, 0), 1.0, glass))
+    world.add(sphere((0, 1, 0), -0.9, glass))
+    world.add(sphere((-4, 1, 0), 1.0, lambertian((0.4, 0.2, 0.1))))
+    world.add(sphere((4, 1, 0), -1.0, metal((0.7, 0.6, 0.5), 0.0)))
+    bubble = dielectric(1.5)
+    world.add(sphere((2, 0.3, 2), (2, 0.6, 2), 0.3, bubble))
+    world.add(sphere((2, 0.3, 2), (2, 0.6, 2), -0.25, bubble))
+    world.add(sphere((-2, 0.4, 2), 0.4, dielectric(1.0 / 1.5)))
+    world.add(sphere((5, 0.3, 1.5), -0.3, lambertian((0.2, 0.6, 0.3))))
+    world.add(sphere((1, 0.35, 3), 0.35, metal((0.8, 0.8, 0.9), 3.0)))
+    return world
+
+
 # ---- mesh configs (BASELINE.json configs 4/5; SURVEY.md §8(d): procedural mesh, since
 # assets/models holds no .obj).  Both read the mesh back through an OBJ file when given
 # one (rt_obj_load), else use meshgen's arrays directly (identical vertices: write_obj

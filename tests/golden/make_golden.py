@@ -1,7 +1,8 @@
 """Generate the golden fixtures in tests/golden/ from the REFERENCE ITSELF.
 
 Run in the build container (where /root/reference exists):
-    make -C oracle ref && python tests/golden/make_golden.py
+    make -C oracle ref && python tests/golden/make_golden.py [COUNTER_CASE ...]
+(with names of COUNTER_CASES: only those goldens are written, every other fixture is left alone)
 
 Every vector here comes out of oracle/_ref/ref_golden, i.e. the unmodified reference
 sources compiled with g++ (oracle/ref_golden.cpp explains the two hooks: RNG injection
@@ -53,6 +54,9 @@ COUNTER_CASES = {
                                              "--vfov", "40", "--defocus-angle", "0"], "stride:5"),
     # PixelMatch scene, whole small frame
     "counter_ground_200x112_4spp": (["--scene", "ground", "--width", "200", "--spp", "4"], "stride:3"),
+    # negative radii: hollow glass, an inside-out metal and lambertian, a moving hollow bubble
+    # (ref_golden.cpp "hollow" = scenes.hollow_glass())
+    "counter_hollow_200x112_4spp": (["--scene", "hollow", "--width", "200", "--spp", "4"], "stride:3"),
 }
 
 
@@ -73,11 +77,8 @@ def parse_render(text: str):
     return ij, sums, rgb, segs, draws, meta
 
 
-def main() -> int:
-    if not REF.exists():
-        print(f"{REF} missing: run `make -C oracle ref` first", file=sys.stderr)
-        return 1
-
+def fixed_fixtures() -> None:
+    """Everything but the counter-RNG goldens."""
     # -- image.ppm (UTF-16LE with CRLF in the reference tree) -------------------------
     raw = Path("/root/reference/image.ppm").read_bytes()
     text = raw.decode("utf-16").replace("\r\n", "\n")
@@ -126,8 +127,23 @@ def main() -> int:
     # -- the random-spheres scene ----------------------------------------------------
     (HERE / "scene_random.txt").write_text(run(["scene"]))
 
+
+def main(only: list[str] | None = None) -> int:
+    if not REF.exists():
+        print(f"{REF} missing: run `make -C oracle ref` first", file=sys.stderr)
+        return 1
+
+    unknown = [n for n in only or [] if n not in COUNTER_CASES]
+    if unknown:
+        print(f"unknown counter case(s) {unknown}: one of {sorted(COUNTER_CASES)}", file=sys.stderr)
+        return 2
+    if not only:
+        fixed_fixtures()
+
     # -- counter-RNG goldens -------------------------------------------------------------
     for name, (args, sel) in COUNTER_CASES.items():
+        if only and name not in only:
+            continue
         if isinstance(sel, tuple):
             _, n, rs = sel
             scene, w = args[args.index("--scene") + 1], int(args[args.index("--width") + 1])
@@ -151,4 +167,4 @@ def main() -> int:
 
 
 if __name__ == "__main__":
-    sys.exit(main())
+    sys.exit(main(sys.argv[1:]))
