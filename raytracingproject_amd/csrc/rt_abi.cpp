@@ -737,6 +737,7 @@ int rt_upload_scene_ex(rt_ctx* c, const rt_sphere* s, int n, const rt_material* 
     bp.cost_traverse = c->tuning.cost_traverse;
     bp.cost_intersect = c->tuning.cost_intersect;
     bp.front = c->tuning.front_spheres;
+    bp.big = relatively_big_spheres(s, n, tri, ntri);
     if (!build_bvh(s, n, bp, bvh, err)) return fail(c, RT_ERR_LIMIT, "%s", err.c_str());
     MeshBvh mbvh;
     const bool gpu_build = ntri > 0 && c->tuning.mesh_builder != RT_MESH_BUILD_HOST;

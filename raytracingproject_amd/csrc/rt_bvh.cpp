@@ -414,6 +414,44 @@ bool build_mesh_bvh(const rt_triangle* tris, int n, int max_leaf, double cost_tr
 
 void sphere_box(const rt_sphere& s, float lo[3], float hi[3]) { to_float_box(exact_box(s), lo, hi); }
 
+std::vector<int> relatively_big_spheres(const rt_sphere* spheres, int n, const rt_triangle* tris, int ntri) {
+    const double inf = std::numeric_limits<double>::infinity();
+    double tlo[3] = {inf, inf, inf}, thi[3] = {-inf, -inf, -inf};
+    for (int k = 0; k < ntri; ++k)
+        for (int a = 0; a < 3; ++a) {
+            tlo[a] = std::fmin(tlo[a], std::fmin(tris[k].v0[a], std::fmin(tris[k].v1[a], tris[k].v2[a])));
+            thi[a] = std::fmax(thi[a], std::fmax(tris[k].v0[a], std::fmax(tris[k].v1[a], tris[k].v2[a])));
+        }
+    std::vector<int> cand;
+    int room = MAX_BIG;
+    for (int k = 0; k < n; ++k) {
+        if (std::fabs(spheres[k].radius) >= BIG_RADIUS)
+            --room;
+        else
+            cand.push_back(k);
+    }
+    std::stable_sort(cand.begin(), cand.end(),
+                     [&](int a, int b) { return std::fabs(spheres[a].radius) > std::fabs(spheres[b].radius); });
+    std::vector<int> big;
+    for (size_t i = 0; i < cand.size() && (int)big.size() < room; ++i) {
+        // the box around the triangles and the spheres after this one
+        double lo[3] = {tlo[0], tlo[1], tlo[2]}, hi[3] = {thi[0], thi[1], thi[2]};
+        for (size_t j = i + 1; j < cand.size(); ++j) {
+            const rt_sphere& q = spheres[cand[j]];
+            const double r = std::fabs(q.radius);
+            for (int a = 0; a < 3; ++a) {
+                const double c1 = q.center[a] + (q.moving ? q.center_vec[a] : 0.0);
+                lo[a] = std::fmin(lo[a], std::fmin(q.center[a], c1) - r);
+                hi[a] = std::fmax(hi[a], std::fmax(q.center[a], c1) + r);
+            }
+        }
+        const double extent = std::fmax(hi[0] - lo[0], std::fmax(hi[1] - lo[1], hi[2] - lo[2]));
+        if (!(extent > 0) || !(std::fabs(spheres[cand[i]].radius) >= BIG_RATIO * extent)) break;   // (nothing else: -inf)
+        big.push_back(cand[i]);
+    }
+    return big;
+}
+
 bool build_bvh(const rt_sphere* spheres, int n, const BvhParams& p, BuiltBvh& out, std::string& err) {
     out = BuiltBvh();
     Builder B(p, out);
@@ -429,7 +467,7 @@ bool build_bvh(const rt_sphere* spheres, int n, const BvhParams& p, BuiltBvh& ou
         }
         // The reference keeps every sphere in one list; very large spheres (radius >=
         // BIG_RADIUS, the R=1000 ground) go to an fp64 side list instead of the BVH.
-        if (std::fabs(s.radius) >= BIG_RADIUS) {
+        if (std::fabs(s.radius) >= BIG_RADIUS || std::find(p.big.begin(), p.big.end(), k) != p.big.end()) {
             out.big.push_back(k);
             continue;
         }

@@ -19,6 +19,8 @@ struct BvhParams {
     int max_leaf = 4;
     int front = 0;                // the `front` largest spheres are tested before the tree, outside it
                                   // (-1: those with radius >= 4x the median, at most 8)
+    std::vector<int> big;         // input indices that join the big class below BIG_RADIUS
+                                  // (relatively_big_spheres)
 };
 
 struct BuiltBvh {
@@ -32,6 +34,12 @@ struct BuiltBvh {
 
 // Returns false (with err) if the scene exceeds the encodable limits of rt_scene.h.
 bool build_bvh(const rt_sphere* spheres, int n, const BvhParams& p, BuiltBvh& out, std::string& err);
+
+// The spheres below BIG_RADIUS that are at least BIG_RATIO times as large as the box around
+// the rest of the scene (rt_scene.h): largest first, each measured against the triangles and
+// the spheres smaller than it (positions over time in [0, 1]), until one is not, or until
+// the big class (those of BIG_RADIUS included) would exceed MAX_BIG.
+std::vector<int> relatively_big_spheres(const rt_sphere* spheres, int n, const rt_triangle* tris, int ntri);
 
 // Uniform grid over the fp32 sphere records [first, n) (rt_scene.h GridHdr): the header and
 // the LDS buffer `out` (cell words, then sphere positions; a multiple of sizeof(Node) bytes:

@@ -141,6 +141,12 @@ constexpr size_t TRIF_SLACK = 128;
 // and are tested in fp64 in every precision: in fp32, c = |oc|^2 - r^2 at |oc| ~ r
 // = 1000 cancels catastrophically (sphere.h:35), SURVEY.md §7 "fp32 precision".
 constexpr double BIG_RADIUS = 64.0;
+// The same cancellation at any scale: a sphere at least BIG_RATIO times as large as the box
+// around everything smaller than it (the other spheres and the triangles) joins that class
+// too -- the R = 1 ground under a scene scaled to millimetres is the R = 1000 ground under
+// the scene in metres (rt_bvh.h relatively_big_spheres).  Scenes whose largest ordinary
+// sphere is smaller than that (all of the reference's) are classified by BIG_RADIUS alone.
+constexpr double BIG_RATIO = 16.0;
 
 // Scene coordinates (centres, motion vectors, radii, vertices) must be finite and within
 // +-COORD_MAX: the builders' SAH areas and the fp32 node boxes stay finite (checked by the
