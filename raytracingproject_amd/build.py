@@ -27,13 +27,15 @@ UNITS = {
                           os.environ.get("RT_F32_CONTRACT", "-ffp-contract=on")],
     "rt_render_f64.hip": ["-ffp-contract=off"],
     "rt_abi.cpp": ["-ffp-contract=off"],
+    "rt_plan.cpp": ["-ffp-contract=off"],
+    "rt_pack.cpp": ["-ffp-contract=off"],
     "rt_bvh.cpp": ["-ffp-contract=off"],
     "rt_obj.cpp": ["-ffp-contract=off"],
     "rt_lbvh.hip": ["-ffp-contract=off"],
     "rt_comm.cpp": [],
 }
 HEADERS = ["rt_device.h", "rt_render_impl.h", "rt_scene.h", "rt_launch.h", "rt_bvh.h", "rt_lbvh.h", "rt_ctx.h",
-           "rt_treelet.h"]
+           "rt_treelet.h", "rt_pack.h"]
 
 
 def _stale(target: Path, deps: list[Path]) -> bool:
@@ -181,6 +183,26 @@ def build_bvh_boxes(verbose: bool = False) -> Path:
             print(" ".join(cmd), flush=True)
         subprocess.run(cmd, check=True)
     return BOXES_EXE
+
+
+PACK_EXE = OBJ / "san" / "pack_driver"
+
+
+def build_pack(verbose: bool = False) -> Path:
+    """tests/cpp/pack_driver.cpp (the host-side scene packing and the sphere grid's reach test;
+    run by tests/test_pack.py) with csrc/rt_pack.cpp and csrc/rt_bvh.cpp, under the same
+    sanitizers as build_sanitize.  No GPU code."""
+    PACK_EXE.parent.mkdir(parents=True, exist_ok=True)
+    srcs = [ROOT / "tests" / "cpp" / "pack_driver.cpp", CSRC / "rt_pack.cpp", CSRC / "rt_bvh.cpp"]
+    deps = srcs + [CSRC / "rt_pack.h", CSRC / "rt_bvh.h", CSRC / "rt_scene.h", ROOT / "include" / "rt_hip.h",
+                   Path(__file__)]
+    if _stale(PACK_EXE, deps):
+        cmd = ["g++", "-std=c++17", *SAN_FLAGS, "-ffp-contract=off", f"-I{ROOT / 'include'}", *map(str, srcs), "-o",
+               str(PACK_EXE), "-lm"]
+        if verbose:
+            print(" ".join(cmd), flush=True)
+        subprocess.run(cmd, check=True)
+    return PACK_EXE
 
 
 def build_oracle(verbose: bool = False) -> None:

@@ -1,5 +1,6 @@
 // rt_ctx.h -- the context behind the C ABI (include/rt_hip.h) and the helpers its
-// implementation files share (rt_abi.cpp: scene, render, frames; rt_comm.cpp: RCCL).
+// implementation files share (rt_abi.cpp: scene, render, frames; rt_plan.cpp: the launch plan;
+// rt_comm.cpp: RCCL).
 // Internal: not installed, not part of the ABI.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -14,6 +15,7 @@
 #include "../../include/rt_hip.h"
 #include "rt_device.h"
 #include "rt_lbvh.h"
+#include "rt_pack.h"
 
 using namespace rtx;
 
@@ -43,13 +45,7 @@ struct rt_ctx {
     GridHdr grid_hdr{};         // its header (RenderParams::grid)
     int grid_entries = 0;       // sphere references over its cells
     double grid_density = 0.0;  // the sphere_grid_density it was built with (rt_scene_info, ABI 10)
-    // r06: where a launch's rays can start (grid_reach_ok, rt_abi.cpp): the box of the
-    // geometry a ray can leave from anywhere on it -- spheres outside the big class, triangles,
-    // and big spheres that refract or move -- and the static opaque big spheres (centre,
-    // radius), which a ray only reaches within its tangent distance
-    double reach_lo[3] = {0, 0, 0}, reach_hi[3] = {0, 0, 0};
-    std::vector<std::array<double, 4>> reach_big;
-    bool grid_blocked = false;  // the current launch's rays could start beyond grid_hdr.far_o: the tree
+    SceneReach reach;           // where a launch's rays can start (rt_pack.h grid_reach_ok)
     // r07: resumable flat grid walks (RenderParams::gsus_lanes / gsus_iters), from the
     // environment's RT_GRID_SUSPEND at rt_create
     int gsus_lanes = GSUS_DEFAULT_LANES, gsus_iters = GSUS_DEFAULT_ITERS;
@@ -140,6 +136,29 @@ inline int grow(rt_ctx* c, void** p, size_t* cap, size_t bytes) {
     *cap = bytes;
     return RT_OK;
 }
+
+// The fp64 kernel (rt_tuning.f64_kernel; 0 = the measured best, rt_render_f64.hip)
+// fp64 kernel: the tuning's, or (0) kernel 5 -- 4 over the sphere grid -- where the scene has
+// a grid and the traversal flags ask for it, else 4; 5 without a grid runs as 4 (the same
+// frame: the grid only picks which spheres are tested)
+// (6, internal: kernel 5 with the flat walk, where the grid is one cell tall in y)
+constexpr int F64_KERNEL_DEFAULT = 4, F64_KERNEL_GRID = 5, F64_KERNEL_GRID_FLAT = 6;
+
+// rt_plan.cpp: the plan of one launch -- which render kernel runs (threads per workgroup,
+// traversal flags, the register-budget key waves_per_eu of its instantiation; fp64: the
+// f64_kernel), the mesh traversal stack entries per lane it keeps in LDS
+// (RenderParams::mstack), its dynamic LDS per workgroup, and the workgroups of it a CU keeps
+// resident (the smaller of the register and LDS limits, at least 1).  grid_in_reach: every ray
+// the launch can start lies within the sphere grid's reach (grid_reach_ok), so a scene with a
+// grid may walk it; queries that belong to no launch plan one within reach.
+struct LaunchPlan {
+    int block, trav, wpe, f64_kernel, mesh_stack;
+    size_t lds_bytes;
+    int wgs_per_cu;
+};
+LaunchPlan plan_launch(const rt_ctx* c, bool grid_in_reach);
+int stack_entries(const rt_ctx* c);
+size_t lds_scene_bytes_at(const rt_ctx* c, int block, int tr = 0);
 
 }  // namespace rtx_abi
 

@@ -835,7 +835,7 @@ __device__ __forceinline__ Hit<R> closest_hit(const SceneView<R>& sc, const Ray<
                 }
             }
             // Termination (r06): every ray origin a launch can produce lies within +-GridHdr::
-            // far_o (rt_abi.cpp grid_reach_ok decides per launch, from the camera and the
+            // far_o (rt_pack.cpp grid_reach_ok decides per launch, from the camera and the
             // scene's bounds; otherwise the launch runs the tree).  There each step moves its
             // axis's plane distance by at least 15/16 of a cell (2^-24 (|o| + ext) stays below
             // cs / 16), so a walk takes at most res[0] + res[1] + res[2] + 2 steps before its

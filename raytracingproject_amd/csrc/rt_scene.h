@@ -61,7 +61,7 @@ struct alignas(16) GridHdr {
     float slab_k;      // (float)n_slab
     int n_slab;        // time slabs (1 .. GRID_SLAB_MAX)
     // The walk's reach (r06, host only -- the kernels never read it): a launch whose rays
-    // can start beyond +-far_o on some axis renders with the tree instead (rt_abi.cpp
+    // can start beyond +-far_o on some axis renders with the tree instead (rt_pack.cpp
     // grid_reach_ok).  Past it the fp32 rounding of the walk's plane distances, which grows
     // as ~(steps + 16) 2^-23 (|o| + the grid's largest coordinate), could exceed the padding
     // of the listed boxes, and far enough out (~2^24 cells) a step no longer moves its plane

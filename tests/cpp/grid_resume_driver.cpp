@@ -262,7 +262,7 @@ int main(int argc, char** argv) {
             }
             const float om = std::fmax(std::fmax(std::fabs((float)ray.o[0]), std::fabs((float)ray.o[1])),
                                        std::fabs((float)ray.o[2]));
-            if (!(om <= hd.far_o)) continue;   // (never walked by the product: rt_abi.cpp grid_reach_ok)
+            if (!(om <= hd.far_o)) continue;   // (never walked by the product: rt_pack.cpp grid_reach_ok)
             double best = INFINITY;
             int best_id = -1;
             for (size_t k = 0; k < sf.size(); ++k) {

@@ -1,0 +1,288 @@
+// pack_driver.cpp -- the host-side scene packing (csrc/rt_pack.cpp pack_scene) and the sphere
+// grid's reach test (grid_reach_ok), built with -fsanitize=address,undefined (build.py
+// build_pack, run by tests/test_pack.py).  No GPU code.
+//
+//   pack_driver SCENE.bin
+//
+// SCENE.bin: int32 n, nm, ntri, ncam; n rt_sphere; nm rt_material; ntri rt_triangle; ncam x
+// (rt_camera, int32 walks, int32 pad).  For fp32 and fp64 x the host and the device mesh
+// builder, pack_scene over the arrays with the context's default tree and grid tuning, then:
+//   * record k is input sphere order[k] converted once (centre, radius, cv zero unless moving,
+//     meta), likewise the big spheres; materials carry albedo and the type's scalar;
+//   * remap is a permutation of the indices it covers (spheres; with the host builder the
+//     triangles too, + n);
+//   * each BigF has |p0 - c| = |r| and |n| = 1 to fp32 rounding, n.(p0 - c) carries the radius'
+//     sign, and inv_r is the same in big and bigf;
+//   * each TriF vertex is the float rounding of its input (TriD: the input), the meta words
+//     match, and at least TRIF_SLACK zero bytes follow the last TriF;
+//   * grid_entries equals the list entries counted from the cell words;
+//   * every sphere outside reach.big and every vertex lies inside the reach box, and every
+//     sphere of reach.big is big, static and opaque;
+//   * box_extent bounds every node box and vertex.
+// Then the rejections (each with its status code), and grid_reach_ok for each camera against
+// the verdict the file states (a scene without a grid never walks).
+#include <algorithm>
+#include <cmath>
+#include <cstdint>
+#include <cstdio>
+#include <cstring>
+#include <limits>
+#include <string>
+#include <vector>
+
+#include "../../raytracingproject_amd/csrc/rt_pack.h"
+
+using namespace rtx;
+
+static long long checks_failed = 0;
+static void check(bool ok, const char* what, int a = -1, int b = -1) {
+    if (!ok && ++checks_failed <= 20) std::printf("CHECK FAILED: %s (%d, %d)\n", what, a, b);
+}
+
+// the fields pack_scene reads, at the context's defaults (rt_ctx.h)
+static rt_tuning tuning_of(int mesh_builder) {
+    rt_tuning t{};
+    t.max_leaf = 6;
+    t.cost_traverse = 1.0;
+    t.cost_intersect = 0.25;
+    t.front_spheres = -1;
+    t.mesh_max_leaf = 2;
+    t.mesh_cost_traverse = 2.0;
+    t.mesh_builder = mesh_builder;
+    t.sphere_grid_density = 2.0;
+    t.sphere_grid_time_slabs = 32;
+    return t;
+}
+
+struct Scene {
+    std::vector<rt_sphere> s;
+    std::vector<rt_material> m;
+    std::vector<rt_triangle> t;
+};
+
+template <class R>
+static void check_sphere_record(const R& r, const rt_sphere& q, const Scene& sc, int k) {
+    using F = decltype(R::r);
+    for (int a = 0; a < 3; ++a) {
+        check(r.c[a] == (F)q.center[a], "a record's centre is the input's, converted once", k, a);
+        check(r.cv[a] == (q.moving ? (F)q.center_vec[a] : (F)0), "cv is the input's where the sphere moves, else zero", k, a);
+    }
+    check(r.r == (F)q.radius, "a record's radius is the input's, converted once", k);
+    check(r.meta == make_meta((uint32_t)q.mat, (uint32_t)sc.m[q.mat].type, q.moving ? 1u : 0u), "a record's meta word", k);
+}
+
+static void check_pack(const Scene& sc, const PackedScene& pk, bool f64, bool gpu) {
+    const int n = (int)sc.s.size(), ntri = (int)sc.t.size(), nb = (int)pk.bvh.order.size();
+    check(pk.f64 == f64 && pk.gpu_build == (gpu && ntri > 0), "the pack states its precision and builder");
+    check((int)(f64 ? pk.sd.size() : pk.sf.size()) == nb && (f64 ? pk.sf.empty() : pk.sd.empty()),
+          "one record per tree sphere, in the context's precision only");
+    for (int k = 0; k < nb; ++k) {
+        if (f64) check_sphere_record(pk.sd[k], sc.s[pk.bvh.order[k]], sc, k);
+        else check_sphere_record(pk.sf[k], sc.s[pk.bvh.order[k]], sc, k);
+    }
+    check((int)(f64 ? pk.md.size() : pk.mf.size()) == (int)sc.m.size(), "one record per material");
+    for (int k = 0; k < (int)sc.m.size(); ++k) {
+        const rt_material& q = sc.m[k];
+        const double x = q.type == RT_METAL ? (q.fuzz < 1 ? q.fuzz : 1) : q.type == RT_DIELECTRIC ? q.ir : 0.0;
+        const double p[4] = {q.albedo[0], q.albedo[1], q.albedo[2], x};
+        for (int a = 0; a < 4; ++a)
+            check(f64 ? pk.md[k].p[a] == p[a] : pk.mf[k].p[a] == (float)p[a], "a material record", k, a);
+    }
+    // remap
+    const size_t covers = (size_t)n + (pk.gpu_build ? 0 : (size_t)ntri);
+    check(pk.remap.size() == covers && (size_t)nb + pk.big.size() == (size_t)n, "remap covers the spheres (+ host-built triangles)");
+    std::vector<int> seen(covers, 0);
+    for (int v : pk.remap)
+        if (v >= 0 && (size_t)v < covers) ++seen[v];
+    for (size_t k = 0; k < covers; ++k) check(seen[k] == 1, "remap is a permutation", (int)k, seen[k]);
+    // big spheres
+    check(pk.big.size() == pk.bvh.big.size() && pk.bigf.size() == pk.big.size(), "a SphereD and a BigF per big sphere");
+    for (size_t k = 0; k < pk.big.size() && k < pk.bigf.size(); ++k) {
+        const rt_sphere& q = sc.s[pk.bvh.big[k]];
+        const BigF& f = pk.bigf[k];
+        check_sphere_record(pk.big[k], q, sc, (int)k);
+        double d2 = 0, n2 = 0, dn = 0, cmax = 0;
+        for (int a = 0; a < 3; ++a) {
+            const double d = (double)f.p0[a] - q.center[a];
+            d2 += d * d;
+            n2 += (double)f.n[a] * f.n[a];
+            dn += d * f.n[a];
+            cmax = std::max(cmax, std::fabs(q.center[a]));
+            check(f.cv[a] == (q.moving ? (float)q.center_vec[a] : 0.f), "BigF cv", (int)k, a);
+        }
+        // (p0's coordinates are fp32 roundings of values within |c_a| + |r|: 2^-24 of that per
+        // axis, sqrt(3) of it on the distance; n's of values within 1: 2^-25 per axis)
+        const double R = std::fabs(q.radius);
+        check(std::fabs(std::sqrt(d2) - R) <= 0x1p-23 * (cmax + R), "BigF: |p0 - c| = |r|", (int)k);
+        check(std::fabs(std::sqrt(n2) - 1.0) <= 0x1p-23, "BigF: |n| = 1", (int)k);
+        check(dn * q.radius > 0, "BigF: n carries the radius' sign", (int)k);
+        check(f.r == (float)q.radius && f.meta == pk.big[k].meta, "BigF radius and meta", (int)k);
+        check(f.inv_r == pk.big[k].inv_r && f.inv_r == (float)(1.0 / q.radius), "inv_r is the same in big and bigf", (int)k);
+    }
+    // triangles
+    if (pk.gpu_build || ntri == 0) {
+        check(pk.tf.empty() && pk.td.empty() && pk.tmeta.empty() && pk.mbvh.order.empty(), "no host triangle records");
+        for (int a = 0; a < 3 && ntri > 0; ++a) check(pk.clo[a] <= pk.chi[a], "centroid bounds are ordered", a);
+    } else {
+        check((int)pk.mbvh.order.size() == ntri, "every triangle in leaf order");
+        check(f64 ? (int)pk.td.size() == ntri && pk.tf.empty()
+                  : pk.tf.size() * sizeof(TriF) >= (size_t)ntri * sizeof(TriF) + TRIF_SLACK && (int)pk.tmeta.size() == ntri,
+              "triangle records (+ TRIF_SLACK)");
+        for (int k = 0; k < ntri && k < (int)pk.mbvh.order.size(); ++k) {
+            const rt_triangle& q = sc.t[pk.mbvh.order[k]];
+            const uint32_t meta = make_meta((uint32_t)q.mat, (uint32_t)sc.m[q.mat].type, 0u);
+            for (int a = 0; a < 3; ++a) {
+                if (f64) check(pk.td[k].v0[a] == q.v0[a] && pk.td[k].e1[a] == q.v1[a] - q.v0[a] &&
+                               pk.td[k].e2[a] == q.v2[a] - q.v0[a], "TriD: v0 and the fp64 edges", k, a);
+                else check(pk.tf[k].v0[a] == (float)q.v0[a] && pk.tf[k].v1[a] == (float)q.v1[a] &&
+                           pk.tf[k].v2[a] == (float)q.v2[a], "TriF: each vertex is the float rounding of its input", k, a);
+            }
+            check(f64 ? pk.td[k].meta == meta : pk.tmeta[k] == meta, "a triangle's meta word", k);
+        }
+        if (!f64) {
+            const unsigned char* p = (const unsigned char*)pk.tf.data();
+            for (size_t b = (size_t)ntri * sizeof(TriF); b < pk.tf.size() * sizeof(TriF); ++b)
+                check(p[b] == 0, "zero bytes follow the last TriF", (int)b);
+        }
+    }
+    // grid
+    if (!pk.grid.empty()) {
+        const GridHdr& h = pk.grid_hdr;
+        const size_t layer = (size_t)h.res[0] * h.res[1];
+        const uint32_t* w = (const uint32_t*)pk.grid.data();
+        check(pk.grid.size() % sizeof(Node) == 0 && (layer * 2 + h.n_cells) * 4 <= pk.grid.size(), "the grid buffer holds its cells");
+        long long entries = 0;
+        for (uint32_t c = 0; c < h.n_cells; ++c) {
+            const uint32_t first = w[layer + c] & GRID_POS_MASK, end = w[layer + c] >> GRID_POS_BITS;
+            check(first <= end && end <= pk.grid.size() && (end - first) % 4 == 0, "a cell's list lies in the buffer", (int)c);
+            entries += (end - first) / 4;
+        }
+        check(entries == pk.grid_entries, "grid_entries counts the cells' list entries", (int)entries, pk.grid_entries);
+    } else {
+        check(pk.grid_entries == 0, "no grid, no entries");
+    }
+    // reach
+    const SceneReach& rc = pk.reach;
+    size_t in_big = 0;
+    for (int k = 0; k < n; ++k) {
+        const rt_sphere& q = sc.s[k];
+        const bool big = std::find(pk.bvh.big.begin(), pk.bvh.big.end(), k) != pk.bvh.big.end();
+        if (big && !q.moving && sc.m[q.mat].type != RT_DIELECTRIC) {
+            ++in_big;
+            continue;
+        }
+        for (int a = 0; a < 3; ++a) {
+            const double c1 = q.center[a] + (q.moving ? q.center_vec[a] : 0.0), R = std::fabs(q.radius);
+            check(rc.lo[a] <= std::min(q.center[a], c1) - R && rc.hi[a] >= std::max(q.center[a], c1) + R,
+                  "the reach box holds every sphere outside reach.big", k, a);
+        }
+    }
+    check(rc.big.size() == in_big, "reach.big: the static opaque big spheres", (int)rc.big.size(), (int)in_big);
+    double ext = 0;
+    for (const rt_triangle& q : sc.t)
+        for (int a = 0; a < 3; ++a)
+            for (double v : {q.v0[a], q.v1[a], q.v2[a]}) {
+                check(rc.lo[a] <= v && v <= rc.hi[a], "the reach box holds every vertex", a);
+                ext = std::max(ext, std::fabs(v));
+            }
+    for (const Node& nd : pk.bvh.nodes)
+        for (int a = 0; a < 3; ++a)
+            for (float v : {nd.lo0[a], nd.hi0[a], nd.lo1[a], nd.hi1[a]}) ext = std::max(ext, (double)std::fabs(v));
+    check(ext <= (double)pk.box_extent, "box_extent bounds every node box and vertex");
+}
+
+static void check_rejections(const Scene& sc) {
+    const rt_tuning t = tuning_of(RT_MESH_BUILD_HOST);
+    const int n = (int)sc.s.size(), nm = (int)sc.m.size(), ntri = (int)sc.t.size();
+    auto run = [&](const Scene& x, int want, const char* what) {
+        PackedScene pk;
+        std::string err;
+        const int rc = pack_scene(x.s.data(), (int)x.s.size(), x.m.data(), (int)x.m.size(), x.t.data(), (int)x.t.size(), t,
+                                  false, pk, err);
+        check(rc == want && !err.empty(), what, rc, want);
+    };
+    Scene x = sc;
+    x.m[0].type = 7;
+    run(x, RT_ERR_INVALID, "material type 7 is RT_ERR_INVALID");
+    if (n > 0) {
+        x = sc;
+        x.s[0].mat = nm;
+        run(x, RT_ERR_INVALID, "a bad material index is RT_ERR_INVALID");
+        x = sc;
+        x.s[n - 1].radius = std::numeric_limits<double>::quiet_NaN();
+        run(x, RT_ERR_INVALID, "a NaN radius is RT_ERR_INVALID");
+        x = sc;
+        x.s[n / 2].center[2] = 1e31;
+        run(x, RT_ERR_LIMIT, "a coordinate of 1e31 is RT_ERR_LIMIT");
+    }
+    if (ntri > 0) {
+        x = sc;
+        x.t[ntri - 1].v1[0] = -1e31;
+        run(x, RT_ERR_LIMIT, "a vertex coordinate of -1e31 is RT_ERR_LIMIT");
+        x = sc;
+        x.t[0].mat = -1;
+        run(x, RT_ERR_INVALID, "a triangle's bad material index is RT_ERR_INVALID");
+    }
+    PackedScene pk;
+    std::string err;
+    int rc = pack_scene(sc.s.data(), n, sc.m.data(), (int)META_MAT_MASK + 1, sc.t.data(), ntri, t, false, pk, err);
+    check(rc == RT_ERR_LIMIT && !err.empty(), "nm > META_MAT_MASK is RT_ERR_LIMIT", rc);
+    rc = pack_scene(nullptr, 1, sc.m.data(), nm, sc.t.data(), ntri, t, false, pk, err);
+    check(rc == RT_ERR_INVALID, "a null sphere array is RT_ERR_INVALID", rc);
+    rc = pack_scene(sc.s.data(), n, nullptr, nm, sc.t.data(), ntri, t, false, pk, err);
+    check(rc == RT_ERR_INVALID, "a null material array is RT_ERR_INVALID", rc);
+    rc = pack_scene(sc.s.data(), n, sc.m.data(), nm, nullptr, 1, t, false, pk, err);
+    check(rc == RT_ERR_INVALID, "a null triangle array is RT_ERR_INVALID", rc);
+    rc = pack_scene(sc.s.data(), -1, sc.m.data(), nm, sc.t.data(), ntri, t, false, pk, err);
+    check(rc == RT_ERR_INVALID, "a negative count is RT_ERR_INVALID", rc);
+}
+
+template <class T>
+static bool read_n(FILE* f, std::vector<T>& v, int n) {
+    v.resize((size_t)n);
+    return n == 0 || std::fread(v.data(), sizeof(T), (size_t)n, f) == (size_t)n;
+}
+
+int main(int argc, char** argv) {
+    if (argc < 2) return 2;
+    Scene sc;
+    struct Cam {
+        rt_camera cam;
+        int32_t walks, pad;
+    };
+    std::vector<Cam> cams;
+    {
+        FILE* f = std::fopen(argv[1], "rb");
+        if (!f) return 2;
+        int32_t h[4];
+        const bool ok = std::fread(h, 4, 4, f) == 4 && h[0] >= 0 && h[1] > 0 && h[2] >= 0 && h[3] >= 0 &&
+                        read_n(f, sc.s, h[0]) && read_n(f, sc.m, h[1]) && read_n(f, sc.t, h[2]) && read_n(f, cams, h[3]);
+        std::fclose(f);
+        if (!ok) return 2;
+    }
+    int packs = 0, grids = 0, big = 0, walks = 0, reach = 0;
+    for (int f64 = 0; f64 < 2; ++f64)
+        for (int builder : {RT_MESH_BUILD_HOST, RT_MESH_BUILD_GPU}) {
+            PackedScene pk;
+            std::string err;
+            const int rc = pack_scene(sc.s.data(), (int)sc.s.size(), sc.m.data(), (int)sc.m.size(), sc.t.data(),
+                                      (int)sc.t.size(), tuning_of(builder), f64 != 0, pk, err);
+            check(rc == RT_OK, err.c_str(), f64, builder);
+            if (rc != RT_OK) continue;
+            check_pack(sc, pk, f64 != 0, builder != RT_MESH_BUILD_HOST);
+            ++packs;
+            grids += !pk.grid.empty();
+            big = (int)pk.big.size();
+            if (f64 || builder != RT_MESH_BUILD_HOST) continue;
+            for (size_t k = 0; k < cams.size(); ++k) {
+                const bool w = !pk.grid.empty() && grid_reach_ok(pk.reach, pk.grid_hdr.far_o, cams[k].cam);
+                check(w == (cams[k].walks != 0), "grid_reach_ok's verdict", (int)k, (int)w);
+                ++reach;
+                walks += w;
+            }
+        }
+    check_rejections(sc);
+    std::printf("pack spheres %zu big %d triangles %zu packs %d grids %d reach %d walks %d checks failed %lld\n", sc.s.size(),
+                big, sc.t.size(), packs, grids, reach, walks, checks_failed);
+    return checks_failed ? 1 : 0;
+}

@@ -254,7 +254,7 @@ int check_grid(const std::vector<SphereF>& sf, int front, double density, int sl
                 }
         }
     // the walk's reach (r06): the kernel walks only launches whose rays all start within
-    // +-far_o (rt_abi.cpp grid_reach_ok), which must cover rays from near the grid
+    // +-far_o (rt_pack.cpp grid_reach_ok), which must cover rays from near the grid
     const int max_steps = hd.res[0] + hd.res[1] + hd.res[2] + 2;
     double gext = 0;
     for (int x = 0; x < 3; ++x) gext = std::max(gext, std::max(std::fabs((double)hd.lo[x]), std::fabs((double)hd.hi[x])));

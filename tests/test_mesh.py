@@ -506,6 +506,43 @@ def test_mesh_auto_plan_matches_the_measured_best():
 
 
 @pytest.mark.gpu
+def test_plan_and_hits_do_not_depend_on_the_previous_launch():
+    """rt_scene_info's plan, rt_set_tuning's LDS verdict and rt_trace_rays' launch are those of a
+    launch within the sphere grid's reach, whatever camera the context rendered from last
+    (ADVICE r06 items 1 and 3): after a render from 150 units out, which the grid's walk does
+    not reach (the tree renders it), the plan fields, lds_bytes and the hits of 4,096 seeded rays
+    are what they were after the upload, mesh_lds_stack = -1 is accepted, and the near camera's
+    frame is a fresh context's bit for bit."""
+    from test_gpu_parity import far_cameras
+    from test_trace_rays import _rays
+    S, M, T = mesh_arrays("mixed")
+    near, far = main_cam(128, 4), far_cameras(150.0)[0].native
+    rays = _rays(4096, seed=3)
+
+    def plan(r):
+        i = r.scene_info()
+        return (i.render_block, i.render_traversal, i.render_waves_per_eu, i.render_mesh_lds_stack, i.lds_bytes)
+
+    with N.Renderer(0, SEED, N.RT_PREC_F32) as r:
+        r.upload_scene(S, M, T)
+        fresh = r.render_frame(near, 4, 50)
+    with N.Renderer(0, SEED, N.RT_PREC_F32) as r:
+        r.upload_scene(S, M, T)
+        before, hits = plan(r), r.trace_rays_host(rays)
+        assert before[1] & N.RT_TRAV_GRID and (hits["id"] >= 0).sum() > 1000
+        assert r.grid_reach(near) and not r.grid_reach(far)
+        r.render_frame(far, 2, 50)
+        assert plan(r) == before
+        again = r.trace_rays_host(rays)
+        for f in ("t", "p", "normal", "id", "front_face", "mat"):
+            assert again[f].tobytes() == hits[f].tobytes(), f
+        r.set_tuning(mesh_lds_stack=-1)
+        assert plan(r) == before
+        out = r.render_frame(near, 4, 50)
+    assert np.array_equal(out[0], fresh[0]) and np.array_equal(out[2], fresh[2])
+
+
+@pytest.mark.gpu
 def test_mesh_kernel_plan_picks_if_if_loop():
     """fp32 mesh scenes run the if-if mesh loop (8192 added to the tuning's flags) unless
     the while-while loop (16384) is asked for; sphere scenes and the fp64 path never carry

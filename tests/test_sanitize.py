@@ -114,7 +114,7 @@ def test_sphere_bvh_and_oracle_under_sanitizers(driver, tmp_path):
     # checked against brute force; every slab box checked to hold its spheres across its slab
     assert int(w[w.index("grids") + 1]) >= 48
     # r06: a quarter of the rays start 10 .. 10^9 cells from the box.  Those within
-    # GridHdr::far_o (the only origins a launch that walks the grid can have: rt_abi.cpp
+    # GridHdr::far_o (the only origins a launch that walks the grid can have: rt_pack.cpp
     # grid_reach_ok) walk exactly, in at most res_x + res_y + res_z + 2 steps, never past the
     # pad layers; those beyond are walked too, under a guard, and some of those walks fail --
     # what the bound is for
