@@ -21,7 +21,7 @@
 extern "C" {
 #endif
 
-#define RT_ABI_VERSION 11
+#define RT_ABI_VERSION 12
 
 enum {
     RT_OK = 0,
@@ -414,6 +414,22 @@ typedef struct {
     int32_t id, front_face, mat, pad;
 } rt_hit;
 int rt_trace_rays(rt_ctx* ctx, const void* rays, int num_rays, rt_hit* hits, void* stream);
+/* ABI 12: rt_trace_rays for rays that may name the primitive they start on.  origin_ids:
+ * device memory, num_rays values in rt_hit.id's numbering (the input index of a sphere,
+ * num_spheres + the input index of a triangle) or -1 for none; any other value counts as -1;
+ * NULL: all -1, which is rt_trace_rays.
+ * fp32 contexts treat primitive origin_ids[i] as the render kernels treat a scattered ray's
+ * previous hit.  The contract: the origin is taken to lie ON that primitive (a hit point of
+ * it, rounded to fp32).  One root of a sphere it starts on is then the origin itself, which
+ * fp32 cannot tell from a hit just above tmin = 0.001 when the direction is short; so that
+ * sphere offers only its other root, t = -2 (o - c).d / d.d -- a hit where it lies in
+ * (0.001, inf): the far side of a sphere the ray enters, nothing for a ray that leaves it --
+ * and that triangle is skipped.  An origin that is not on the named primitive gets that
+ * same treatment, which is then not the closest hit.
+ * fp64 contexts ignore the ids: the reference has no such notion (sphere.h:41-46 tests both
+ * roots against tmin), and the records equal rt_trace_rays' bit for bit. */
+int rt_trace_rays_from(rt_ctx* ctx, const void* rays, int num_rays, const int32_t* origin_ids, rt_hit* hits,
+                       void* stream);
 /* The same, instrumented (fp32 sphere scenes; synchronous): counters = {node-loop wave
  * iterations, their active lanes, sphere-loop wave iterations, their active lanes}. */
 int rt_trace_rays_diag(rt_ctx* ctx, const void* rays, int num_rays, rt_hit* hits, uint64_t counters[4]);

@@ -15,7 +15,7 @@ import os
 LIB_PATH = Path(os.environ.get("RT_LIB_PATH", Path(__file__).resolve().parent / "lib" / "librt_hip.so"))
 
 RT_OK, RT_ERR_INVALID, RT_ERR_HIP, RT_ERR_NO_SCENE, RT_ERR_LIMIT, RT_ERR_COMM = 0, -1, -2, -3, -4, -5
-RT_ABI_VERSION = 11
+RT_ABI_VERSION = 12
 RT_TRAV_SELROOT, RT_TRAV_B128, RT_TRAV_COH = 8, 16, 64   # rt_hip.h traversal flags
 RT_TRAV_NOSUM, RT_TRAV_TBIN, RT_TRAV_CULL, RT_TRAV_MTOP, RT_TRAV_MIFIF, RT_TRAV_MWHILE = 128, 256, 512, 4096, 8192, 16384
 RT_TRAV_MQ = 32768
@@ -135,6 +135,7 @@ SIGNATURES = {
     "rt_trace_tape": (C.c_int, [C.c_void_p, C.POINTER(C.c_double), C.c_int, C.POINTER(C.c_double), C.c_int,
                                 C.POINTER(C.c_double), C.POINTER(C.c_int)]),
     "rt_trace_rays": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
+    "rt_trace_rays_from": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
     "rt_trace_rays_diag": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.POINTER(C.c_uint64)]),
 }
 
@@ -449,15 +450,32 @@ class Renderer:
         self._check(self._L.rt_trace_rays(self.ctx, C.c_void_p(rays_dev), n, C.c_void_p(hits_dev),
                                           C.c_void_p(stream or 0)), "rt_trace_rays")
 
-    def trace_rays_host(self, rays: np.ndarray) -> np.ndarray:
-        """rt_trace_rays through device copies: rays[n, 7] (context precision) -> HIT_DTYPE[n]."""
+    def trace_rays_from(self, rays_dev: int, n: int, origin_ids_dev: int, hits_dev: int,
+                        stream: int | None = None) -> None:
+        """rt_trace_rays_from: rt_trace_rays with, per ray, the id of the primitive it starts on
+        (n int32 in rt_hit.id's numbering, device; a null pointer: none)."""
+        self._check(self._L.rt_trace_rays_from(self.ctx, C.c_void_p(rays_dev), n, C.c_void_p(origin_ids_dev or 0),
+                                               C.c_void_p(hits_dev), C.c_void_p(stream or 0)), "rt_trace_rays_from")
+
+    def trace_rays_host(self, rays: np.ndarray, origin_ids: np.ndarray | None = None) -> np.ndarray:
+        """rt_trace_rays through device copies: rays[n, 7] (context precision) -> HIT_DTYPE[n];
+        with origin_ids[n] (rt_hit.id's numbering, -1 for none), rt_trace_rays_from."""
         import torch
         rays = np.ascontiguousarray(rays, dtype=self.dtype).reshape(-1, 7)
         n = len(rays)
         d_rays = torch.from_numpy(rays).to("cuda")
         d_hits = torch.empty(max(1, n) * HIT_DTYPE.itemsize, dtype=torch.uint8, device="cuda")
-        torch.cuda.synchronize()
-        self.trace_rays(d_rays.data_ptr(), n, d_hits.data_ptr(), torch.cuda.current_stream().cuda_stream)
+        stream = torch.cuda.current_stream().cuda_stream
+        if origin_ids is None:
+            torch.cuda.synchronize()
+            self.trace_rays(d_rays.data_ptr(), n, d_hits.data_ptr(), stream)
+        else:
+            ids = np.ascontiguousarray(origin_ids, dtype=np.int32).reshape(-1)
+            if len(ids) != n:
+                raise ValueError(f"origin_ids holds {len(ids)} ids for {n} rays")
+            d_ids = torch.from_numpy(ids if n else np.zeros(1, np.int32)).to("cuda")
+            torch.cuda.synchronize()
+            self.trace_rays_from(d_rays.data_ptr(), n, d_ids.data_ptr(), d_hits.data_ptr(), stream)
         torch.cuda.synchronize()
         return d_hits.cpu().numpy()[: n * HIT_DTYPE.itemsize].view(HIT_DTYPE)
 

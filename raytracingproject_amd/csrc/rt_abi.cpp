@@ -43,6 +43,9 @@ void free_scene(rt_ctx* c) {
     (void)hipFree(c->d_tmeta);
     (void)hipFree(c->d_remap);
     c->d_remap = nullptr;
+    (void)hipFree(c->d_unmap);
+    c->d_unmap = nullptr;
+    c->n_unmap = 0;
     (void)hipFree(c->d_grid);
     c->d_grid = nullptr;
     c->grid_nodes = c->grid_entries = 0;
@@ -463,8 +466,11 @@ static int upload_packed(rt_ctx* c, PackedScene& pk, int n, const rt_material* m
         std::vector<uint32_t> perm((size_t)ntri);
         HIPCHK(c, hipMemcpy(perm.data(), lbvh_sorted_index(c->lbvh, ntri), (size_t)ntri * 4, hipMemcpyDeviceToHost));
         for (uint32_t k : perm) pk.remap.push_back(n + (int)k);
+        invert_remap(pk.remap, (int)pk.bvh.order.size(), (int)pk.big.size(), n + ntri, pk.unmap);
     }
     if ((rc = upload((void**)&c->d_remap, pk.remap.data(), pk.remap.size() * sizeof(int))) != RT_OK) return rc;
+    if ((rc = upload((void**)&c->d_unmap, pk.unmap.data(), pk.unmap.size() * sizeof(int))) != RT_OK) return rc;
+    c->n_unmap = (int)pk.unmap.size();
     c->box_extent = pk.box_extent;
     c->reach = pk.reach;
     c->n_nodes = (int)pk.bvh.nodes.size();
@@ -954,7 +960,8 @@ int rt_render_frame_multi(rt_ctx** cs, int n, const rt_camera* cam, int spp, int
     return RT_OK;
 }
 
-static int trace_rays(rt_ctx* c, const void* rays, int n, rt_hit* hits, void* stream, unsigned long long* diag) {
+static int trace_rays(rt_ctx* c, const void* rays, int n, const int32_t* origin_ids, rt_hit* hits, void* stream,
+                      unsigned long long* diag) {
     if (!c) return RT_ERR_INVALID;
     if (!c->has_scene) return fail(c, RT_ERR_NO_SCENE, "rt_trace_rays before rt_upload_scene");
     if (n < 0 || (n > 0 && (!rays || !hits))) return fail(c, RT_ERR_INVALID, "rt_trace_rays: %d rays, rays %p, hits %p", n, rays, hits);
@@ -969,8 +976,10 @@ static int trace_rays(rt_ctx* c, const void* rays, int n, rt_hit* hits, void* st
     if (lds > 160 * 1024) return fail(c, RT_ERR_LIMIT, "rt_trace_rays needs %zu B of LDS per workgroup", lds);
     hipStream_t st = stream ? (hipStream_t)stream : c->stream;
     HIPCHK(c, hipEventRecord(c->ev0, st));
-    const hipError_t e = c->precision == RT_PREC_F64 ? launch_trace_f64(P, lds, st, rays, n, hits, c->d_remap)
-                                                     : launch_trace_f32(P, lds, st, rays, n, hits, c->d_remap, diag != nullptr);
+    const hipError_t e =
+        c->precision == RT_PREC_F64
+            ? launch_trace_f64(P, lds, st, rays, n, hits, c->d_remap, origin_ids, c->d_unmap, c->n_unmap)
+            : launch_trace_f32(P, lds, st, rays, n, hits, c->d_remap, origin_ids, c->d_unmap, c->n_unmap, diag != nullptr);
     if (e != hipSuccess) return fail(c, RT_ERR_HIP, "trace launch: %s", hipGetErrorString(e));
     HIPCHK(c, hipEventRecord(c->ev1, st));
     c->timed = true;
@@ -978,7 +987,11 @@ static int trace_rays(rt_ctx* c, const void* rays, int n, rt_hit* hits, void* st
 }
 
 int rt_trace_rays(rt_ctx* c, const void* rays, int n, rt_hit* hits, void* stream) {
-    return trace_rays(c, rays, n, hits, stream, nullptr);
+    return trace_rays(c, rays, n, nullptr, hits, stream, nullptr);
+}
+
+int rt_trace_rays_from(rt_ctx* c, const void* rays, int n, const int32_t* origin_ids, rt_hit* hits, void* stream) {
+    return trace_rays(c, rays, n, origin_ids, hits, stream, nullptr);
 }
 
 int rt_trace_rays_diag(rt_ctx* c, const void* rays, int n, rt_hit* hits, uint64_t counters[4]) {
@@ -988,7 +1001,7 @@ int rt_trace_rays_diag(rt_ctx* c, const void* rays, int n, rt_hit* hits, uint64_
     unsigned long long* d = nullptr;
     HIPCHK(c, hipMalloc((void**)&d, DIAG_SLOTS * sizeof(unsigned long long)));
     hipError_t e = hipMemsetAsync(d, 0, DIAG_SLOTS * sizeof(unsigned long long), c->stream);
-    int rc = e == hipSuccess ? trace_rays(c, rays, n, hits, c->stream, d) : RT_OK;
+    int rc = e == hipSuccess ? trace_rays(c, rays, n, nullptr, hits, c->stream, d) : RT_OK;
     unsigned long long h[DIAG_SLOTS] = {};
     if (e == hipSuccess && rc == RT_OK) e = hipMemcpyAsync(h, d, sizeof(h), hipMemcpyDeviceToHost, c->stream);
     if (e == hipSuccess && rc == RT_OK) e = hipStreamSynchronize(c->stream);

@@ -50,6 +50,8 @@ struct rt_ctx {
     // environment's RT_GRID_SUSPEND at rt_create
     int gsus_lanes = GSUS_DEFAULT_LANES, gsus_iters = GSUS_DEFAULT_ITERS;
     int* d_remap = nullptr;     // rt_trace_rays: kernel id slot -> input index (spheres | big | triangles)
+    int* d_unmap = nullptr;     // rt_trace_rays_from: input index -> Hit::id (d_remap's inverse), n_unmap entries
+    int n_unmap = 0;
     Node4* d_mnodes = nullptr;  // mesh BVH (4-wide) + triangles (HBM-resident)
     void* d_tris = nullptr;
     uint32_t* d_tmeta = nullptr;   // fp32: per-triangle meta words (leaf order), beside the 48-B TriF records

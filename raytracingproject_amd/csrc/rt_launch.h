@@ -32,12 +32,15 @@ bool render_f32_diag_supported(int block, int waves_per_eu, int trav, bool mesh)
 hipError_t launch_render_f32_diag(const RenderParams& P, size_t lds_bytes, hipStream_t stream, int trav, int block,
                                   int waves_per_eu);
 hipError_t launch_render_f64(const RenderParams& P, size_t lds_bytes, hipStream_t stream, int kernel);
-// batched world.hit (rt_trace_rays): n rays of 7 values (context precision) -> n rt_hit
+// batched world.hit (rt_trace_rays, rt_trace_rays_from): n rays of 7 values (context precision)
+// -> n rt_hit; origin_ids: null, or per ray the input id of the primitive it starts on, looked
+// up in unmap (n_unmap entries)
 constexpr int TRACE_BLOCK = 256;
 hipError_t launch_trace_f32(const RenderParams& P, size_t lds_bytes, hipStream_t stream, const void* rays, int n,
-                            void* hits, const int* remap, bool diag);
+                            void* hits, const int* remap, const int* origin_ids, const int* unmap, int n_unmap,
+                            bool diag);
 hipError_t launch_trace_f64(const RenderParams& P, size_t lds_bytes, hipStream_t stream, const void* rays, int n,
-                            void* hits, const int* remap);
+                            void* hits, const int* remap, const int* origin_ids, const int* unmap, int n_unmap);
 hipError_t launch_tape_f64(const RenderParams& P, int max_depth, const double* ray7, const double* tape, int tape_len,
                            double* out, int* used, hipStream_t stream);
 // element: 4 (float/uint32) or 8 (double); channels: 1 or 3

@@ -332,7 +332,14 @@ int pack_scene(const rt_sphere* s, int n, const rt_material* m, int nm, const rt
     for (int k = 0; k < nb; ++k) out.remap.push_back(bvh.order[k]);
     for (int k : bvh.big) out.remap.push_back(k);
     for (int k : mbvh.order) out.remap.push_back(n + k);
+    if (!out.gpu_build) invert_remap(out.remap, nb, (int)out.big.size(), n + ntri, out.unmap);
     return RT_OK;
+}
+
+void invert_remap(const std::vector<int>& remap, int n_spheres, int n_big, int total, std::vector<int>& unmap) {
+    unmap.assign((size_t)std::max(total, 0), NO_SELF);
+    for (size_t slot = 0; slot < remap.size(); ++slot)
+        if (remap[slot] >= 0 && remap[slot] < total) unmap[(size_t)remap[slot]] = kernel_id_of_slot((int)slot, n_spheres, n_big);
 }
 
 }  // namespace rtx

@@ -1,6 +1,6 @@
 // rt_pack.h -- a scene's host-side packing: everything rt_upload_scene_ex computes before it
 // touches the device (argument checks, the trees, the per-precision records, the sphere grid,
-// rt_trace_rays' id map, the walk's reach), and the reach test each launch makes against it.
+// rt_trace_rays' id map and its inverse, the walk's reach), and the reach test each launch makes against it.
 // Host only, no HIP types: built with g++ under the sanitizers by tests/cpp/pack_driver.cpp.
 #pragma once
 #include <array>
@@ -44,10 +44,16 @@ struct PackedScene {
     GridHdr grid_hdr{};
     int grid_entries = 0;              // sphere references over its cells
     std::vector<int> remap;            // kernel id slot -> input index: spheres | big | host-built triangles (+ n)
+    std::vector<int> unmap;            // remap's inverse (invert_remap); with gpu_build: the caller, once remap is whole
     SceneReach reach;
     float box_extent = 0.f;            // bound of |coordinate| over the node boxes and vertices
     double clo[3] = {0, 0, 0}, chi[3] = {0, 0, 0};   // gpu_build: the triangle centroids' bounds (Morton grid)
 };
+
+// rt_trace_rays_from's id map, remap's inverse: input index (spheres, then n + triangle) -> Hit::id
+// (kernel_id_of_slot of the slot that holds it), NO_SELF for an index remap does not hold.
+// remap: n_spheres tree positions | n_big big spheres | triangles; `total` input primitives.
+void invert_remap(const std::vector<int>& remap, int n_spheres, int n_big, int total, std::vector<int>& unmap);
 
 // Checks the arrays and packs them for a context of the given precision and tuning (the tree,
 // grid and mesh-builder fields).  RT_OK, or the status rt_upload_scene_ex returns with its

@@ -96,7 +96,8 @@ hipError_t launch_render_f32_diag(const RenderParams& P, size_t lds_bytes, hipSt
 // (select root, whole-record LDS reads for spheres, pop culling; meshes: the if-if mesh
 // loop); DIAG counts loop utilisation (tools/sort_bound.py).
 hipError_t launch_trace_f32(const RenderParams& P, size_t lds_bytes, hipStream_t stream, const void* rays, int n,
-                            void* hits, const int* remap, bool diag) {
+                            void* hits, const int* remap, const int* origin_ids, const int* unmap, int n_unmap,
+                            bool diag) {
     if (n <= 0) return hipSuccess;
     constexpr int B = TRACE_BLOCK;
     const int grid = std::min((n + B - 1) / B, 8192);
@@ -105,13 +106,13 @@ hipError_t launch_trace_f32(const RenderParams& P, size_t lds_bytes, hipStream_t
     TraceHit* h = (TraceHit*)hits;
     if (P.n_mnodes > 0)
         hipLaunchKernelGGL((trace_kernel<float, false, B, TM, true>), dim3(grid), dim3(B), lds_bytes, stream, P, r, n, h,
-                           remap);
+                           remap, origin_ids, unmap, n_unmap);
     else if (diag)
         hipLaunchKernelGGL((trace_kernel<float, false, B, TS, false, true>), dim3(grid), dim3(B), lds_bytes, stream, P,
-                           r, n, h, remap);
+                           r, n, h, remap, origin_ids, unmap, n_unmap);
     else
         hipLaunchKernelGGL((trace_kernel<float, false, B, TS, false>), dim3(grid), dim3(B), lds_bytes, stream, P, r, n,
-                           h, remap);
+                           h, remap, origin_ids, unmap, n_unmap);
     return hipGetLastError();
 }
 

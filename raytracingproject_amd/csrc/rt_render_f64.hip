@@ -228,7 +228,7 @@ __global__ void reconcile_accum_kernel(const float* __restrict__ out, long long*
 
 // Batched world.hit (rt_trace_rays), fp64: the reference's arithmetic (sphere.h:30-57).
 hipError_t launch_trace_f64(const RenderParams& P, size_t lds_bytes, hipStream_t stream, const void* rays, int n,
-                            void* hits, const int* remap) {
+                            void* hits, const int* remap, const int* origin_ids, const int* unmap, int n_unmap) {
     if (n <= 0) return hipSuccess;
     constexpr int B = TRACE_BLOCK;
     const int grid = (n + B - 1) / B < 8192 ? (n + B - 1) / B : 8192;
@@ -237,10 +237,10 @@ hipError_t launch_trace_f64(const RenderParams& P, size_t lds_bytes, hipStream_t
     // the default fp64 kernel's box tests (conservative fp32 slabs)
     if (P.n_mnodes > 0)
         hipLaunchKernelGGL((trace_kernel<double, true, B, TRAV_F32BOX, true>), dim3(grid), dim3(B), lds_bytes, stream,
-                           P, r, n, h, remap);
+                           P, r, n, h, remap, origin_ids, unmap, n_unmap);
     else
         hipLaunchKernelGGL((trace_kernel<double, true, B, TRAV_F32BOX, false>), dim3(grid), dim3(B), lds_bytes, stream,
-                           P, r, n, h, remap);
+                           P, r, n, h, remap, origin_ids, unmap, n_unmap);
     return hipGetLastError();
 }
 

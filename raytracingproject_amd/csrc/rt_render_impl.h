@@ -8,8 +8,6 @@
 
 namespace rtx {
 
-constexpr int NO_SELF = 0x7fffffff;
-
 // Path radiance and pixel sums with explicit rounding: FP contraction may not fuse
 // `acc + thr * L` differently in different inlined copies of the loop, so a frame split
 // into sample ranges (rt_render_range) sums bit-identically to one launch.
@@ -999,7 +997,10 @@ __global__ __attribute__((amdgpu_flat_work_group_size(1, BLOCK), amdgpu_waves_pe
 // (hit_record, hittable.h:7-22: p, normal, front_face, material) -- shade() -- written per
 // ray.  ids are mapped back to the caller's input order (remap: BVH sphere position ->
 // input index; big sphere k -> remap[n_spheres + k]; triangle k (BVH leaf order) ->
-// remap[n_spheres + n_big + k]).  DIAG counts the node / sphere loop lane utilisation.
+// remap[n_spheres + n_big + k]).  origin_ids (rt_trace_rays_from; null: none): per ray, the
+// input id of the primitive it starts on, -1 for none, looked up in `unmap` (remap's inverse,
+// n_unmap entries; any id outside it: none); fp32 then offers that sphere's far root only and
+// skips that triangle, fp64 ignores it.  DIAG counts the node / sphere loop lane utilisation.
 // ---------------------------------------------------------------------------------
 struct TraceHit {   // = rt_hit (include/rt_hip.h)
     double t, p[3], normal[3];
@@ -1009,7 +1010,9 @@ static_assert(sizeof(TraceHit) == 72, "rt_hit");
 
 template <class R, bool EXACT, int BLOCK, int TRAV, bool MESH, bool DIAG = false>
 __global__ __launch_bounds__(BLOCK) void trace_kernel(RenderParams P, const R* __restrict__ rays, int n,
-                                                      TraceHit* __restrict__ hits, const int* __restrict__ remap) {
+                                                      TraceHit* __restrict__ hits, const int* __restrict__ remap,
+                                                      const int* __restrict__ origin_ids,
+                                                      const int* __restrict__ unmap, int n_unmap) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     uint16_t* s_stack;
     uint32_t* s_mstack;
@@ -1025,7 +1028,10 @@ __global__ __launch_bounds__(BLOCK) void trace_kernel(RenderParams P, const R* _
         ray.o = mk(q[0], q[1], q[2]);
         ray.d = mk(q[3], q[4], q[5]);
         ray.time = q[6];
-        const Hit<R> h = closest_hit<R, EXACT, DIAG, TRAV, MESH>(sc, ray, stack, BLOCK, NO_SELF, &dg);
+        // rt_trace_rays_from: the primitive the ray starts on, as the render kernels' previous
+        // hit (fp64 has no such notion: sphere.h tests every sphere against tmin alone)
+        const int self = !EXACT && origin_ids ? origin_kernel_id(unmap, n_unmap, origin_ids[i]) : NO_SELF;
+        const Hit<R> h = closest_hit<R, EXACT, DIAG, TRAV, MESH>(sc, ray, stack, BLOCK, self, &dg);
         TraceHit o{};
         o.id = -1;
         if (h.id != -1) {

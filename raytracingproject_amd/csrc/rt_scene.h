@@ -110,6 +110,28 @@ constexpr int MESH_STACK_MAX = 64;       // per-lane scratch stack entries
 constexpr int MESH_TOP_MAX = 4096;       // breadth-first prefix of the node array (LDS-cacheable)
 constexpr int MESH_HIT_BASE = 0x40000000;  // Hit::id of triangle k = MESH_HIT_BASE | k
 
+// The primitive a ray starts on, in Hit::id's numbering (closest_hit's self_id): NO_SELF for none.
+constexpr int NO_SELF = 0x7fffffff;
+#ifndef RT_HD
+#ifdef __HIPCC__
+#define RT_HD __host__ __device__
+#else
+#define RT_HD
+#endif
+#endif
+// Hit::id of the primitive in slot `slot` of rt_trace_rays' id map (remap: n_spheres tree
+// positions | n_big big spheres | triangles in leaf order)
+RT_HD inline int kernel_id_of_slot(int slot, int n_spheres, int n_big) {
+    return slot < n_spheres ? slot : slot < n_spheres + n_big ? -2 - (slot - n_spheres)
+                                                             : MESH_HIT_BASE | (slot - n_spheres - n_big);
+}
+// rt_trace_rays_from: the Hit::id of the caller's origin id (rt_hit.id's numbering: input sphere
+// index, n_input_spheres + triangle) through the inverse map `unmap` of `total` entries;
+// NO_SELF for -1 and for every other id outside [0, total), and without a map
+RT_HD inline int origin_kernel_id(const int* unmap, int total, int id) {
+    return unmap && id >= 0 && id < total ? unmap[id] : NO_SELF;
+}
+
 // Mesh BVH node: 4 children, SoA boxes (one 128-B L2 line), refs as MREF_* (EMPTY slots
 // carry an inverted box).  4-wide halves the dependent node-load chain of a binary tree.
 struct alignas(16) Node4 {

@@ -11,6 +11,9 @@
 //     meta), likewise the big spheres; materials carry albedo and the type's scalar;
 //   * remap is a permutation of the indices it covers (spheres; with the host builder the
 //     triangles too, + n);
+//   * unmap inverts remap: input index -> Hit::id (tree position, -2 - k for big sphere k,
+//     MESH_HIT_BASE | leaf position), and origin_kernel_id answers NO_SELF for -1, INT_MIN and
+//     the total count;
 //   * each BigF has |p0 - c| = |r| and |n| = 1 to fp32 rounding, n.(p0 - c) carries the radius'
 //     sign, and inv_r is the same in big and bigf;
 //   * each TriF vertex is the float rounding of its input (TriD: the input), the meta words
@@ -95,6 +98,36 @@ static void check_pack(const Scene& sc, const PackedScene& pk, bool f64, bool gp
     for (int v : pk.remap)
         if (v >= 0 && (size_t)v < covers) ++seen[v];
     for (size_t k = 0; k < covers; ++k) check(seen[k] == 1, "remap is a permutation", (int)k, seen[k]);
+    // unmap, remap's inverse: every slot's input index maps back to that slot's Hit::id -- a tree
+    // position for a sphere, -2 - k for big sphere k, MESH_HIT_BASE | leaf position for a
+    // triangle -- and the lookup refuses every id outside [0, n + ntri).  (A device-built tree's
+    // triangle part is the caller's: here the triangles reversed stand in for its leaf order.)
+    {
+        std::vector<int> remap = pk.remap, unmap = pk.unmap;
+        const int total = n + ntri, nbig = (int)pk.big.size();
+        if (pk.gpu_build) {
+            check(unmap.empty(), "a device-built tree's unmap is left to the caller");
+            for (int k = 0; k < ntri; ++k) remap.push_back(n + (ntri - 1 - k));
+            invert_remap(remap, nb, nbig, total, unmap);
+        }
+        check((int)unmap.size() == total && (int)remap.size() == total, "unmap holds every input primitive", (int)unmap.size(), total);
+        const int* um = unmap.data();
+        for (int slot = 0; slot < (int)remap.size() && (int)unmap.size() == total; ++slot) {
+            const int id = origin_kernel_id(um, total, remap[slot]);
+            const int want = slot < nb ? slot : slot < nb + nbig ? -2 - (slot - nb) : (MESH_HIT_BASE | (slot - nb - nbig));
+            check(id == want && id == kernel_id_of_slot(slot, nb, nbig), "unmap[remap[slot]] is the slot's Hit::id", slot, id);
+            check(slot < nb + nbig ? remap[slot] < n : remap[slot] >= n, "spheres and triangles keep their id ranges", slot);
+        }
+        for (size_t k = 0; k < pk.bvh.big.size() && (int)unmap.size() == total; ++k)
+            check(origin_kernel_id(um, total, pk.bvh.big[k]) == -2 - (int)k, "a big sphere's Hit::id is -2 - k", (int)k);
+        for (int k = 0; k < ntri && !pk.gpu_build && (int)unmap.size() == total; ++k)
+            check(origin_kernel_id(um, total, n + pk.mbvh.order[k]) == (MESH_HIT_BASE | k), "a triangle's Hit::id is its leaf position", k);
+        check(origin_kernel_id(um, total, -1) == NO_SELF, "origin id -1 names nothing");
+        check(origin_kernel_id(um, total, std::numeric_limits<int>::min()) == NO_SELF, "origin id INT_MIN names nothing");
+        check(origin_kernel_id(um, total, total) == NO_SELF, "origin id n + ntri names nothing");
+        check(origin_kernel_id(um, total, std::numeric_limits<int>::max()) == NO_SELF, "origin id INT_MAX names nothing");
+        check(origin_kernel_id(nullptr, total, 0) == NO_SELF, "no map, no origin");
+    }
     // big spheres
     check(pk.big.size() == pk.bvh.big.size() && pk.bigf.size() == pk.big.size(), "a SphereD and a BigF per big sphere");
     for (size_t k = 0; k < pk.big.size() && k < pk.bigf.size(); ++k) {

@@ -16,6 +16,7 @@ fp32 -- an eps-correct closest hit (check_fp32): the triangle reported must be o
 Rays and meshes are generated from seeds; every triangle gets material k mod (number of
 materials), so that a record's material names its triangle.  The references are computed
 once per class and cached for the module."""
+import copy
 import ctypes as C
 
 import numpy as np
@@ -478,7 +479,7 @@ def case32(name):
     return _CASES32[name]
 
 
-def check_fp32(c, h):
+def check_fp32(c, h, skip=None):
     """The rule an fp32 answer h (HIT_DTYPE records) must satisfy for every ray of class c:
     -> (why, other_sphere): why[i] is '' where ray i passes, else the first rule it breaks;
     other_sphere marks the rays that report a sphere other than the reference's (the caller
@@ -490,7 +491,14 @@ def check_fp32(c, h):
                 |p - (o + t64(k) d)| <= tol |d|; normal within 1e-6 of + or - the fp64 unit
                 normal of k and against d; front_face the reference's for k (the last two
                 unless |nd| is within its bound); mat = T.mat[k]; id the input index of k.
-    sphere:     the reference's sphere, |t - t_s| <= tol, t_s <= t* + tol."""
+    sphere:     the reference's sphere, |t - t_s| <= tol, t_s <= t* + tol.
+    skip:       per ray, the triangle it starts on (rt_trace_rays_from; -1: none), which is no
+                candidate: a certain miss, and t* the smallest over the others."""
+    if skip is not None:
+        c, masked = copy.copy(c), np.flatnonzero(skip >= 0)
+        c.cmiss, c.chit = c.cmiss.copy(), c.chit.copy()
+        c.cmiss[masked, skip[masked]], c.chit[masked, skip[masked]] = True, False
+        c.tstar = np.minimum(np.where(c.chit, c.t64, np.inf).min(axis=1), np.where(c.sid >= 0, c.ts, np.inf))
     n, nS, m = len(c.rays), len(c.S), len(c.T)
     o, d = c.rays[:, 0:3], c.rays[:, 3:6]
     r = np.arange(n)
