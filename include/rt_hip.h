@@ -430,6 +430,27 @@ int rt_trace_rays(rt_ctx* ctx, const void* rays, int num_rays, rt_hit* hits, voi
  * roots against tmin), and the records equal rt_trace_rays' bit for bit. */
 int rt_trace_rays_from(rt_ctx* ctx, const void* rays, int num_rays, const int32_t* origin_ids, rt_hit* hits,
                        void* stream);
+/* Batched any-hit visibility: hittable::hit's return value (hittable.h:28) for num_rays rays,
+ * each over its own interval: occluded[i] = 1 where some primitive of the uploaded world has a
+ * root t with tmin_i < t < tmax_i (interval::surrounds, interval.h:33-35), else 0.  No record:
+ * shadow rays, ambient occlusion, line of sight, "anything within distance L".
+ * rays: as for rt_trace_rays.  intervals: device memory, num_rays records {tmin, tmax} of the
+ * context precision; NULL: (0.001, +inf) for every ray.  occluded: device memory, num_rays
+ * bytes, each written 0 or 1.  tmax = +inf is valid; so is a negative or -inf tmin (the
+ * reference's interval has no sign rule: roots behind the origin count where the interval
+ * admits them).  tmin >= tmax, or a NaN end, gives 0 and is no error.  A ray that starts on a
+ * surface passes a tmin; there are no origin ids here.
+ * fp64 contexts return the reference's boolean exactly (sphere.h:30-48's roots, both tested);
+ * fp32 contexts run the primitive tests of rt_trace_rays, so with intervals = NULL the answer
+ * is (rt_hit.id != -1) ray for ray.  The traversal stops at a ray's first hit, orders nothing
+ * and writes one byte, where rt_trace_rays finds the closest hit and writes 72.
+ * Errors as rt_trace_rays (RT_ERR_NO_SCENE before an upload, RT_ERR_INVALID for num_rays < 0
+ * or a NULL rays / occluded with num_rays > 0, RT_ERR_LIMIT past 160 KiB of LDS); num_rays ==
+ * 0 is a no-op.  Asynchronous on `stream` (NULL: the context's); rt_last_kernel_ms times it.
+ * Added to ABI 12 without a version bump: a new entry point changes no existing one, so every
+ * caller built against 12 keeps working, and one that needs rt_occluded looks the symbol up. */
+int rt_occluded(rt_ctx* ctx, const void* rays, int num_rays, const void* intervals, uint8_t* occluded,
+                void* stream);
 /* The same, instrumented (fp32 sphere scenes; synchronous): counters = {node-loop wave
  * iterations, their active lanes, sphere-loop wave iterations, their active lanes}. */
 int rt_trace_rays_diag(rt_ctx* ctx, const void* rays, int num_rays, rt_hit* hits, uint64_t counters[4]);

@@ -137,6 +137,7 @@ SIGNATURES = {
     "rt_trace_rays": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
     "rt_trace_rays_from": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
     "rt_trace_rays_diag": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.POINTER(C.c_uint64)]),
+    "rt_occluded": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),   # ABI 12
 }
 
 # rt_hit (72 B): rt_trace_rays' per-ray hit record
@@ -478,6 +479,36 @@ class Renderer:
             self.trace_rays_from(d_rays.data_ptr(), n, d_ids.data_ptr(), d_hits.data_ptr(), stream)
         torch.cuda.synchronize()
         return d_hits.cpu().numpy()[: n * HIT_DTYPE.itemsize].view(HIT_DTYPE)
+
+    def occluded(self, rays_dev: int, n: int, intervals_dev: int | None, out_dev: int,
+                 stream: int | None = None) -> None:
+        """rt_occluded: n rays (7 values each, device) over n intervals {tmin, tmax} (device; a null
+        pointer: (0.001, inf) for every ray) -> n bytes, 1 where something lies inside the interval."""
+        self._check(self._L.rt_occluded(self.ctx, C.c_void_p(rays_dev or 0), n, C.c_void_p(intervals_dev or 0),
+                                        C.c_void_p(out_dev or 0), C.c_void_p(stream or 0)), "rt_occluded")
+
+    def occluded_host(self, rays: np.ndarray, intervals: np.ndarray | None = None) -> np.ndarray:
+        """rt_occluded through device copies: rays[n, 7] and intervals[n, 2] (context precision;
+        None: (0.001, inf) for every ray) -> bool[n]."""
+        import torch
+        rays = np.ascontiguousarray(rays, dtype=self.dtype).reshape(-1, 7)
+        n = len(rays)
+        d_rays = torch.from_numpy(rays).to("cuda")
+        d_iv = None
+        if intervals is not None:
+            iv = np.ascontiguousarray(intervals, dtype=self.dtype).reshape(-1, 2)
+            if len(iv) != n:
+                raise ValueError(f"intervals holds {len(iv)} records for {n} rays")
+            d_iv = torch.from_numpy(iv if n else np.zeros((1, 2), self.dtype)).to("cuda")
+        d_out = torch.full((max(1, n),), 255, dtype=torch.uint8, device="cuda")
+        stream = torch.cuda.current_stream().cuda_stream
+        torch.cuda.synchronize()
+        self.occluded(d_rays.data_ptr(), n, d_iv.data_ptr() if d_iv is not None else None, d_out.data_ptr(), stream)
+        torch.cuda.synchronize()
+        out = d_out.cpu().numpy()[:n]
+        if n and out.max() > 1:
+            raise RtError(f"rt_occluded wrote byte {int(out.max())}")
+        return out.astype(bool)
 
     def trace_rays_diag(self, rays_dev: int, n: int, hits_dev: int) -> dict:
         c = (C.c_uint64 * 4)()

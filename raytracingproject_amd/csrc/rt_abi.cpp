@@ -960,20 +960,28 @@ int rt_render_frame_multi(rt_ctx** cs, int n, const rt_camera* cam, int spp, int
     return RT_OK;
 }
 
+// The per-ray query launches (rt_trace_rays*, rt_occluded): the scene's tree in LDS at
+// TRACE_BLOCK threads, and its size there with the mesh stack's LDS columns.
+static int query_setup(rt_ctx* c, const char* what, RenderParams& P, size_t& lds) {
+    HIPCHK(c, hipSetDevice(c->device));
+    rt_camera cam{};
+    cam.image_width = cam.image_height = 1;
+    fill_params(c, &cam, 1, 1, plan_launch(c, true).mesh_stack, P);
+    P.nodes = c->d_nodes;   // (the time-binned copies are a render-kernel option)
+    lds = lds_scene_bytes_at(c, TRACE_BLOCK) + (size_t)TRACE_BLOCK * (size_t)P.mstack * 4;
+    if (lds > 160 * 1024) return fail(c, RT_ERR_LIMIT, "%s needs %zu B of LDS per workgroup", what, lds);
+    return RT_OK;
+}
+
 static int trace_rays(rt_ctx* c, const void* rays, int n, const int32_t* origin_ids, rt_hit* hits, void* stream,
                       unsigned long long* diag) {
     if (!c) return RT_ERR_INVALID;
     if (!c->has_scene) return fail(c, RT_ERR_NO_SCENE, "rt_trace_rays before rt_upload_scene");
     if (n < 0 || (n > 0 && (!rays || !hits))) return fail(c, RT_ERR_INVALID, "rt_trace_rays: %d rays, rays %p, hits %p", n, rays, hits);
-    HIPCHK(c, hipSetDevice(c->device));
     RenderParams P;
-    rt_camera cam{};
-    cam.image_width = cam.image_height = 1;
-    fill_params(c, &cam, 1, 1, plan_launch(c, true).mesh_stack, P);
-    P.nodes = c->d_nodes;   // (the time-binned copies are a render-kernel option)
+    size_t lds;
+    if (int rc = query_setup(c, "rt_trace_rays", P, lds)) return rc;
     P.diag = diag;
-    const size_t lds = lds_scene_bytes_at(c, TRACE_BLOCK) + (size_t)TRACE_BLOCK * (size_t)P.mstack * 4;
-    if (lds > 160 * 1024) return fail(c, RT_ERR_LIMIT, "rt_trace_rays needs %zu B of LDS per workgroup", lds);
     hipStream_t st = stream ? (hipStream_t)stream : c->stream;
     HIPCHK(c, hipEventRecord(c->ev0, st));
     const hipError_t e =
@@ -992,6 +1000,24 @@ int rt_trace_rays(rt_ctx* c, const void* rays, int n, rt_hit* hits, void* stream
 
 int rt_trace_rays_from(rt_ctx* c, const void* rays, int n, const int32_t* origin_ids, rt_hit* hits, void* stream) {
     return trace_rays(c, rays, n, origin_ids, hits, stream, nullptr);
+}
+
+int rt_occluded(rt_ctx* c, const void* rays, int n, const void* intervals, uint8_t* occluded, void* stream) {
+    if (!c) return RT_ERR_INVALID;
+    if (!c->has_scene) return fail(c, RT_ERR_NO_SCENE, "rt_occluded before rt_upload_scene");
+    if (n < 0 || (n > 0 && (!rays || !occluded)))
+        return fail(c, RT_ERR_INVALID, "rt_occluded: %d rays, rays %p, occluded %p", n, rays, (void*)occluded);
+    RenderParams P;
+    size_t lds;
+    if (int rc = query_setup(c, "rt_occluded", P, lds)) return rc;
+    hipStream_t st = stream ? (hipStream_t)stream : c->stream;
+    HIPCHK(c, hipEventRecord(c->ev0, st));
+    const hipError_t e = c->precision == RT_PREC_F64 ? launch_occluded_f64(P, lds, st, rays, n, intervals, occluded)
+                                                     : launch_occluded_f32(P, lds, st, rays, n, intervals, occluded);
+    if (e != hipSuccess) return fail(c, RT_ERR_HIP, "occlusion launch: %s", hipGetErrorString(e));
+    HIPCHK(c, hipEventRecord(c->ev1, st));
+    c->timed = true;
+    return RT_OK;
 }
 
 int rt_trace_rays_diag(rt_ctx* c, const void* rays, int n, rt_hit* hits, uint64_t counters[4]) {

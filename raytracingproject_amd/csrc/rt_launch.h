@@ -41,6 +41,12 @@ hipError_t launch_trace_f32(const RenderParams& P, size_t lds_bytes, hipStream_t
                             bool diag);
 hipError_t launch_trace_f64(const RenderParams& P, size_t lds_bytes, hipStream_t stream, const void* rays, int n,
                             void* hits, const int* remap, const int* origin_ids, const int* unmap, int n_unmap);
+// batched any-hit visibility (rt_occluded): n rays as above, intervals: null (every ray over
+// (0.001, inf)) or n records {tmin, tmax} of the context precision -> n bytes, 0 or 1
+hipError_t launch_occluded_f32(const RenderParams& P, size_t lds_bytes, hipStream_t stream, const void* rays, int n,
+                               const void* intervals, uint8_t* occluded);
+hipError_t launch_occluded_f64(const RenderParams& P, size_t lds_bytes, hipStream_t stream, const void* rays, int n,
+                               const void* intervals, uint8_t* occluded);
 hipError_t launch_tape_f64(const RenderParams& P, int max_depth, const double* ray7, const double* tape, int tape_len,
                            double* out, int* used, hipStream_t stream);
 // element: 4 (float/uint32) or 8 (double); channels: 1 or 3

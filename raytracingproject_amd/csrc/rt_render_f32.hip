@@ -4,7 +4,7 @@
 // denormals flushed; the parity tests bound the effect (<= 2 LSB vs the reference).
 #include <algorithm>
 
-#include "rt_render_impl.h"
+#include "rt_occluded.h"   // (includes rt_render_impl.h)
 
 namespace rtx {
 
@@ -113,6 +113,25 @@ hipError_t launch_trace_f32(const RenderParams& P, size_t lds_bytes, hipStream_t
     else
         hipLaunchKernelGGL((trace_kernel<float, false, B, TS, false>), dim3(grid), dim3(B), lds_bytes, stream, P, r, n,
                            h, remap, origin_ids, unmap, n_unmap);
+    return hipGetLastError();
+}
+
+// Batched any-hit visibility (rt_occluded), fp32: launch_trace_f32's traversal flags, so that
+// the primitive and box tests are the closest-hit query's instantiations.
+hipError_t launch_occluded_f32(const RenderParams& P, size_t lds_bytes, hipStream_t stream, const void* rays, int n,
+                               const void* intervals, uint8_t* occluded) {
+    if (n <= 0) return hipSuccess;
+    constexpr int B = TRACE_BLOCK;
+    const int grid = std::min((n + B - 1) / B, 8192);
+    constexpr int TS = TRAV_SELROOT | TRAV_B128 | TRAV_CULL, TM = TRAV_SELROOT | TRAV_CULL | TRAV_MIFIF;
+    const float* r = (const float*)rays;
+    const float* iv = (const float*)intervals;
+    if (P.n_mnodes > 0)
+        hipLaunchKernelGGL((occluded_kernel<float, false, B, TM, true>), dim3(grid), dim3(B), lds_bytes, stream, P, r,
+                           n, iv, occluded);
+    else
+        hipLaunchKernelGGL((occluded_kernel<float, false, B, TS, false>), dim3(grid), dim3(B), lds_bytes, stream, P, r,
+                           n, iv, occluded);
     return hipGetLastError();
 }
 

@@ -1,7 +1,7 @@
 // rt_render_f64.hip -- fp64 reference-exact path, built with -ffp-contract=off so every
 // operation rounds as in the g++ build of the reference.  Also hosts the small
 // precision-agnostic kernels (unshard, quantize).
-#include "rt_render_impl.h"
+#include "rt_occluded.h"   // (includes rt_render_impl.h)
 
 namespace rtx {
 
@@ -241,6 +241,24 @@ hipError_t launch_trace_f64(const RenderParams& P, size_t lds_bytes, hipStream_t
     else
         hipLaunchKernelGGL((trace_kernel<double, true, B, TRAV_F32BOX, false>), dim3(grid), dim3(B), lds_bytes, stream,
                            P, r, n, h, remap, origin_ids, unmap, n_unmap);
+    return hipGetLastError();
+}
+
+// Batched any-hit visibility (rt_occluded), fp64: the reference's boolean (hittable.h:28) --
+// spheres and triangles in its fp64 arithmetic, conservative fp32 boxes that only prune.
+hipError_t launch_occluded_f64(const RenderParams& P, size_t lds_bytes, hipStream_t stream, const void* rays, int n,
+                               const void* intervals, uint8_t* occluded) {
+    if (n <= 0) return hipSuccess;
+    constexpr int B = TRACE_BLOCK;
+    const int grid = (n + B - 1) / B < 8192 ? (n + B - 1) / B : 8192;
+    const double* r = (const double*)rays;
+    const double* iv = (const double*)intervals;
+    if (P.n_mnodes > 0)
+        hipLaunchKernelGGL((occluded_kernel<double, true, B, TRAV_F32BOX, true>), dim3(grid), dim3(B), lds_bytes,
+                           stream, P, r, n, iv, occluded);
+    else
+        hipLaunchKernelGGL((occluded_kernel<double, true, B, TRAV_F32BOX, false>), dim3(grid), dim3(B), lds_bytes,
+                           stream, P, r, n, iv, occluded);
     return hipGetLastError();
 }
 
