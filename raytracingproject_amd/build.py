@@ -35,7 +35,7 @@ UNITS = {
     "rt_comm.cpp": [],
 }
 HEADERS = ["rt_device.h", "rt_render_impl.h", "rt_occluded.h", "rt_scene.h", "rt_launch.h", "rt_bvh.h", "rt_lbvh.h", "rt_ctx.h",
-           "rt_treelet.h", "rt_pack.h"]
+           "rt_treelet.h", "rt_pack.h", "rt_batch_cull.h"]
 
 
 def _stale(target: Path, deps: list[Path]) -> bool:
@@ -203,6 +203,34 @@ def build_pack(verbose: bool = False) -> Path:
             print(" ".join(cmd), flush=True)
         subprocess.run(cmd, check=True)
     return PACK_EXE
+
+
+CULL_EXE = OBJ / "san" / "batch_cull_driver"
+CULL_MUTANTS = (1, 2, 3)   # rt_batch_cull.h RT_CULL_MUTATE: no margins, no lens radius, no motion half-length
+
+
+def build_batch_cull(verbose: bool = False) -> list[Path]:
+    """tests/cpp/batch_cull_driver.cpp (the tile / sphere cull of csrc/rt_batch_cull.h against
+    brute force over fp64 camera rays; run by tests/test_batch_cull.py) under the same sanitizers
+    as build_sanitize: the driver itself, then one copy per mutation of the predicate, each of
+    which the driver must catch.  No GPU code."""
+    CULL_EXE.parent.mkdir(parents=True, exist_ok=True)
+    src = ROOT / "tests" / "cpp" / "batch_cull_driver.cpp"
+    deps = [src, CSRC / "rt_batch_cull.h", CSRC / "rt_scene.h", Path(__file__)]
+    exes = [CULL_EXE] + [CULL_EXE.with_name(f"batch_cull_driver_m{m}") for m in CULL_MUTANTS]
+
+    def one(k: int) -> None:
+        if _stale(exes[k], deps):
+            # (-O2 after SAN_FLAGS' -O1: the brute force is a billion flops)
+            cmd = ["g++", "-std=c++17", *SAN_FLAGS, "-O2", "-ffp-contract=off", f"-DRT_CULL_MUTATE={k}", f"-I{CSRC}", str(src),
+                   "-o", str(exes[k]), "-lm"]
+            if verbose:
+                print(" ".join(cmd), flush=True)
+            subprocess.run(cmd, check=True)
+
+    with ThreadPoolExecutor(max_workers=4) as ex:
+        list(ex.map(one, range(len(exes))))
+    return exes
 
 
 def build_oracle(verbose: bool = False) -> None:

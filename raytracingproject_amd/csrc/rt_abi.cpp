@@ -175,6 +175,19 @@ static bool parse_grid_suspend(const char* s, int& lanes, int& iters) {
     return false;
 }
 
+// RT_BATCH_CULL: "0" (every camera-ray batch walks the grid) or the candidate lists' cap,
+// 1..BATCH_CAND_CAP; unset or empty keeps the default.  Like RT_GRID_SUSPEND no rt_tuning
+// field: the frame does not depend on it.
+static bool parse_batch_cull(const char* s, int& cap) {
+    if (!s || !*s) return true;
+    int v = 0, n = 0;
+    if (sscanf(s, "%d%n", &v, &n) == 1 && !s[n] && v >= 0 && v <= BATCH_CAND_CAP) {
+        cap = v;
+        return true;
+    }
+    return false;
+}
+
 rt_ctx* rt_create(int device, uint64_t seed, int precision) {
     if (precision != RT_PREC_F32 && precision != RT_PREC_F64) return nullptr;
     int n = 0;
@@ -183,6 +196,11 @@ rt_ctx* rt_create(int device, uint64_t seed, int precision) {
     rt_ctx* c = new rt_ctx();
     if (!parse_grid_suspend(getenv("RT_GRID_SUSPEND"), c->gsus_lanes, c->gsus_iters)) {
         fprintf(stderr, "rt_create: RT_GRID_SUSPEND must be \"0\" or \"LANES,ITERS\" (1..64, 1..65535)\n");
+        delete c;
+        return nullptr;
+    }
+    if (!parse_batch_cull(getenv("RT_BATCH_CULL"), c->batch_cap)) {
+        fprintf(stderr, "rt_create: RT_BATCH_CULL must be 0..%d\n", BATCH_CAND_CAP);
         delete c;
         return nullptr;
     }
@@ -642,6 +660,8 @@ static int render_range_f32(rt_ctx* c, const LaunchPlan& plan, RenderParams P, s
     P.diag = c->diag_buf;
     P.gsus_lanes = c->gsus_lanes;
     P.gsus_iters = c->gsus_iters;
+    P.batch_cap = c->batch_cap;
+    P.batch_pad = 0;
     if (!slot->queue) HIPCHK(c, hipMalloc((void**)&slot->queue, QUEUE_CTRL_BYTES));
     P.queue = slot->queue;
     {

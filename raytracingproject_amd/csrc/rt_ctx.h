@@ -49,6 +49,9 @@ struct rt_ctx {
     // r07: resumable flat grid walks (RenderParams::gsus_lanes / gsus_iters), from the
     // environment's RT_GRID_SUSPEND at rt_create
     int gsus_lanes = GSUS_DEFAULT_LANES, gsus_iters = GSUS_DEFAULT_ITERS;
+    // r09: per-item candidate lists (RenderParams::batch_cap), from the environment's
+    // RT_BATCH_CULL at rt_create
+    int batch_cap = BATCH_CAND_CAP;
     int* d_remap = nullptr;     // rt_trace_rays: kernel id slot -> input index (spheres | big | triangles)
     int* d_unmap = nullptr;     // rt_trace_rays_from: input index -> Hit::id (d_remap's inverse), n_unmap entries
     int n_unmap = 0;

@@ -13,6 +13,7 @@
 #include <cstdint>
 
 #include "rt_scene.h"
+#include "rt_batch_cull.h"
 
 
 namespace rtx {
@@ -206,6 +207,11 @@ struct RenderParams {
     // rt_create): between blocks of gsus_iters iterations the lanes still walking suspend once
     // they are at most gsus_lanes (0: never)
     int gsus_lanes, gsus_iters;
+    // per-item candidate lists (r09, render_coherent's batches in the fp32 sphere-grid kernels;
+    // the environment's RT_BATCH_CULL at rt_create): an item whose tile's camera rays can reach
+    // at most batch_cap spheres (rt_batch_cull.h) tests those instead of walking the grid;
+    // 0: never (every batch walks), at most BATCH_CAND_CAP
+    int batch_cap, batch_pad;
 };
 // (the defaults: profiles/r07/cpu/grid_resume_bound_r07.txt, then measured: DESIGN.md §5 r07)
 constexpr int GSUS_DEFAULT_LANES = 16, GSUS_DEFAULT_ITERS = 8;
@@ -261,11 +267,12 @@ constexpr size_t COH_SUM_BYTES = 64 * 3 * sizeof(float);   // the wave's item pi
 // mixed-scene kernels (coh_parks)
 constexpr size_t COH_PARK_BYTES = 64 * 4 * sizeof(float);
 // LDS per wave of the coherent kernel: the FIFO, then (unless TRAV_NOSUM, or fp64) the item
-// sums, then (coh_parks) the parked path state
-constexpr size_t coh_wave_bytes(bool mesh, bool sums, int fifo = COH_FIFO, bool f64 = false, bool park = false) {
+// sums, then (coh_parks) the parked path state, then (coh_cands) the item's candidate list
+constexpr size_t coh_wave_bytes(bool mesh, bool sums, int fifo = COH_FIFO, bool f64 = false, bool park = false,
+                                bool cand = false) {
     return (size_t)fifo * (f64 ? (mesh ? sizeof(CohEntryD<true>) : sizeof(CohEntryD<false>))
                                : (mesh ? sizeof(CohEntryT<true>) : sizeof(CohEntryT<false>))) +
-           (sums && !f64 ? COH_SUM_BYTES : 0) + (park ? COH_PARK_BYTES : 0);
+           (sums && !f64 ? COH_SUM_BYTES : 0) + (park ? COH_PARK_BYTES : 0) + (cand ? BATCH_CAND_BYTES : 0);
 }
 constexpr size_t COH_WAVE_BYTES = coh_wave_bytes(false, true);
 // per workgroup: the kernel's rarely read constants (camera vectors, work-queue phases),
@@ -621,6 +628,10 @@ constexpr int coh_fifo_entries(int) { return COH_FIFO; }
 // (profiles/r06/r06p).  Mesh-only C4 keeps them in registers: parked it ran 42.9-44.9 ms
 // against 39.8-40.0 at every block and LDS stack depth tried (r06q).
 constexpr bool coh_parks(bool mesh, int tr, bool f64) { return mesh && !f64 && (tr & TRAV_GRID) != 0; }
+// r09: the fp32 sphere-only kernels over the sphere grid keep a per-wave list of the spheres
+// the current item's camera rays can reach (BATCH_CAND_BYTES; rt_batch_cull.h).  The tree
+// kernels, at 79.6 of the 80 KB that let two workgroups share a CU, have no room for it.
+constexpr bool coh_cands(bool mesh, int tr, bool f64) { return !mesh && !f64 && (tr & TRAV_GRID) != 0; }
 // LDS views by 32-bit LDS byte address (the sphere grid's flat walk and record reads)
 typedef __attribute__((address_space(3))) const uint32_t lds_cu32;
 typedef __attribute__((address_space(3))) const float4 lds_cf4;
@@ -631,12 +642,20 @@ __device__ __forceinline__ void keep_live(uint32_t v) { asm volatile("" ::"v"(v)
 // distance a suspended walk of this ray stopped at, with its closest hit so far in *part.
 // On return *resume >= 0 says that this walk was suspended there (the returned hit is then
 // the closest so far), < 0 that it is complete.  sus_lanes / sus_iters: RenderParams.
-template <class R, bool EXACT, bool DIAG = false, int TRAV = 0, bool MESH = false, bool SUSP = false>
+// CAND (r09, render_coherent's batches in the coh_cands kernels): after the big spheres the
+// ncand sphere records whose LDS byte offsets stand at LDS address clist are tested, and
+// nothing else -- no front list, no grid.  The caller's list holds every sphere of the LDS
+// array the ray can hit (rt_batch_cull.h), the test is test_rec with the walk's arguments,
+// and the closest hit does not depend on the order of the tests: the walk's hit, bit for bit.
+template <class R, bool EXACT, bool DIAG = false, int TRAV = 0, bool MESH = false, bool SUSP = false,
+          bool CAND = false>
 __device__ __forceinline__ Hit<R> closest_hit(const SceneView<R>& sc, const Ray<R>& ray, uint16_t* stack, int stride,
                                               int self_id, DiagCounters* dg = nullptr, float* resume = nullptr,
-                                              const Hit<R>* part = nullptr, int sus_lanes = 0, int sus_iters = 0) {
+                                              const Hit<R>* part = nullptr, int sus_lanes = 0, int sus_iters = 0,
+                                              uint32_t clist = 0, int ncand = 0) {
     static_assert(!SUSP || (!EXACT && !MESH && (TRAV & TRAV_GRID) != 0 && (TRAV & TRAV_GFLAT) != 0),
                   "resumable walks: the fp32 sphere-only flat grid walk");
+    static_assert(!CAND || (!SUSP && coh_cands(MESH, TRAV, EXACT)), "candidate lists: the fp32 sphere-grid kernels");
     constexpr R TMIN = (R)0.001;
     Hit<R> h;
     h.id = -1;
@@ -730,6 +749,26 @@ __device__ __forceinline__ Hit<R> closest_hit(const SceneView<R>& sc, const Ray<
                                      ray.time, TMIN, tlim, !EXACT && is_self, tk);
     };
     auto test_one = [&](int k, R tlim, R& tk) -> bool { return test_rec(sc.sph + k, k == self_id, tlim, tk); };
+    if constexpr (CAND) {
+        // one record per iteration, the same for every lane: the list entry and the record
+        // are read from wave-uniform LDS addresses, the loop count is scalar
+        uint32_t hit_off = 0xffffffffu;
+        for (int i = 0; i < ncand; ++i) {
+            if (DIAG) DiagCounters::count(dg->leaf_it, dg->leaf_act), ++dg->steps;
+            const uint32_t off = (uint32_t)__builtin_amdgcn_readfirstlane(
+                (int)*(const lds_cu32*)(uintptr_t)(clist + 4u * (uint32_t)i));
+            const Sph* rec = (const Sph*)(const float4*)(const lds_cf4*)(uintptr_t)off;
+            R t;
+            if (test_rec(rec, false, tmax, t)) {
+                tmax = t;
+                hit_off = off;
+            }
+        }
+        if (hit_off != 0xffffffffu)
+            h.id = (int)((hit_off - (uint32_t)sc.n_nodes * (uint32_t)sizeof(Node)) / (uint32_t)sizeof(Sph));
+        h.t = tmax;
+        return h;
+    }
     // front list (rt_tuning.front_spheres): the largest spheres, tested by every lane
     // before the tree; the closest hit is the same in any test order
     for (int k = 0; k < (SUSP && resumed ? 0 : sc.n_front); ++k) {

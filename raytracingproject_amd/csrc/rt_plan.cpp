@@ -83,7 +83,9 @@ struct Planner {
         const size_t nw = (size_t)(block / 64);
         const size_t coh = c->n_mnodes > 0 || !(tr & TRAV_COH)
                                ? 0
-                               : nw * coh_wave_bytes(false, (tr & TRAV_NOSUM) == 0, coh_fifo_entries(tr), !f32) + COH_CAM_BYTES;
+                               : nw * coh_wave_bytes(false, (tr & TRAV_NOSUM) == 0, coh_fifo_entries(tr), !f32, false,
+                                                    coh_cands(false, tr, !f32)) +
+                                     COH_CAM_BYTES;
         return lds_scene_bytes_at(c, block, tr) + coh;
     }
 
@@ -192,8 +194,9 @@ struct Planner {
             if ((t & TRAV_COH) && !(t & TRAV_NOSUM)) {
                 const size_t base = lds_scene_bytes_at(c, b, t), nw = (size_t)(b / 64);
                 const int fifo = coh_fifo_entries(t);
-                const size_t with = base + nw * coh_wave_bytes(false, true, fifo) + COH_CAM_BYTES,
-                             without = base + nw * coh_wave_bytes(false, false, fifo) + COH_CAM_BYTES;
+                const bool cand = coh_cands(false, t, false);   // (fp32 here: the grid kernels' lists)
+                const size_t with = base + nw * coh_wave_bytes(false, true, fifo, false, false, cand) + COH_CAM_BYTES,
+                             without = base + nw * coh_wave_bytes(false, false, fifo, false, false, cand) + COH_CAM_BYTES;
                 // (occupancy counts registers too: a small scene whose sums only lower a
                 // workgroup count the registers never reach keeps them)
                 const int reg = wgs_per_cu_bt(b, t, w);

@@ -473,6 +473,13 @@ __device__ __forceinline__ void render_coherent(const RenderParams& P0, const Sc
     };
     constexpr int FIFO = coh_fifo_entries(TRAV);       // primary hits the wave's FIFO holds
     const int lane = threadIdx.x & 63;
+    // r09: the current item's candidate spheres (rt_batch_cull.h), as the LDS byte offsets of
+    // their records in ascending order, and at word BATCH_CAND_CAP their count (negative: the
+    // item walks the grid) -- in LDS after the FIFO and the item sums, so that the bounce loop
+    // carries no register for it
+    constexpr bool CAND = coh_cands(MESH, TRAV, EXACT);
+    [[maybe_unused]] uint32_t* const clist =
+        (uint32_t*)((unsigned char*)fifo + (size_t)FIFO * sizeof(CohEntryX<R, MESH>) + (SUMS ? COH_SUM_BYTES : 0));
     DiagCounters dg, dgb;
     unsigned long long n_bounce = 0, n_live = 0, cyc_trav = 0, cyc_shade = 0, cyc_batch = 0, n_paths = 0, n_seg = 0,
                        n_batch = 0, n_pop = 0;
@@ -538,6 +545,31 @@ __device__ __forceinline__ void render_coherent(const RenderParams& P0, const Sc
                 if (DIAG) rt_dry = __builtin_amdgcn_s_memrealtime();
                 return;
             }
+            if constexpr (CAND) {
+                // the new item's list: lane l tests records l, l + 64, ... of the LDS sphere
+                // array (front list included) against the tile's beam; survivors are compacted
+                // in index order.  More than batch_cap of them (or batch_cap 0): the item walks.
+                const int cap = P.batch_cap;
+                uint32_t n = 0xffffffffu;
+                if (cap > 0) {
+                    const CullBeam bm = cull_beam(cam, P.defocus, cur.tx0, cur.ty0);
+                    const int nsph = P.n_spheres;
+                    const uint32_t sph0 = (uint32_t)sc.n_nodes * (uint32_t)sizeof(Node);
+                    n = 0;
+                    for (int b0 = 0; b0 < nsph; b0 += 64) {
+                        const int k = b0 + lane;
+                        const bool keep = k < nsph && cull_keep(bm, sc.sph[k]);
+                        const unsigned long long km = __ballot(keep);
+                        const uint32_t r = n + __builtin_amdgcn_mbcnt_hi((uint32_t)(km >> 32),
+                                                                         __builtin_amdgcn_mbcnt_lo((uint32_t)km, 0u));
+                        if (keep && r < (uint32_t)BATCH_CAND_CAP) clist[r] = sph0 + (uint32_t)k * (uint32_t)sizeof(SphereF);
+                        n += (uint32_t)__popcll(km);
+                    }
+                    if (n > (uint32_t)cap) n = 0xffffffffu;
+                }
+                if (lane == 0) clist[BATCH_CAND_CAP] = n;
+                __builtin_amdgcn_wave_barrier();
+            }
         }
         const int s = cur.s0 + bi++;
         const int px = cur.tx0 + (lane & 7), py = cur.ty0 + (lane >> 3);
@@ -551,7 +583,17 @@ __device__ __forceinline__ void render_coherent(const RenderParams& P0, const Sc
             CounterRng r2;
             r2.start(hash32(P.seed32 ^ (uint32_t)(py * P.W + px)), (uint32_t)s);
             const Ray<R> pr = KDEF ? cam_ray(px, py, r2, -1, &kd) : cam_ray(px, py, r2);
-            hb = closest_hit<R, EXACT, DIAG, TR, MESH>(sc, pr, stack, BLOCK, NO_SELF, &dgb);
+            if constexpr (CAND) {
+                // (wave-uniform: the item's count, one LDS word)
+                const int nc = __builtin_amdgcn_readfirstlane((int)clist[BATCH_CAND_CAP]);
+                if (nc >= 0)
+                    hb = closest_hit<R, EXACT, DIAG, TR, MESH, false, true>(sc, pr, stack, BLOCK, NO_SELF, &dgb, nullptr,
+                                                                            nullptr, 0, 0, (uint32_t)(uintptr_t)clist, nc);
+                else
+                    hb = closest_hit<R, EXACT, DIAG, TR, MESH>(sc, pr, stack, BLOCK, NO_SELF, &dgb);
+            } else {
+                hb = closest_hit<R, EXACT, DIAG, TR, MESH>(sc, pr, stack, BLOCK, NO_SELF, &dgb);
+            }
             if (hb.id == -1) {   // sky: the path ends here (camera_cpu.h:23-25 with attenuation 1)
                 finish(pp, true, sky(pr.d), 1u, (uint32_t)(s - P.sample_begin));
             } else {
@@ -920,7 +962,8 @@ __global__ __attribute__((amdgpu_flat_work_group_size(1, BLOCK), amdgpu_waves_pe
     if constexpr ((TRAV & TRAV_COH) != 0) {
         // the camera vectors and phase tables (CohConst), after the per-wave regions
         constexpr size_t WB =
-            coh_wave_bytes(MESH, (TRAV & TRAV_NOSUM) == 0, coh_fifo_entries(TRAV), EXACT, coh_parks(MESH, TRAV, EXACT));
+            coh_wave_bytes(MESH, (TRAV & TRAV_NOSUM) == 0, coh_fifo_entries(TRAV), EXACT, coh_parks(MESH, TRAV, EXACT),
+                           coh_cands(MESH, TRAV, EXACT));
         CohConst* kc = (CohConst*)((unsigned char*)(s_mstack + (size_t)BLOCK * P.mstack) + (size_t)(BLOCK / 64) * WB);
         if (tid == 0) {
 #pragma unroll
@@ -971,7 +1014,8 @@ __global__ __attribute__((amdgpu_flat_work_group_size(1, BLOCK), amdgpu_waves_pe
         // coherent primaries: per wave a FIFO of primary hits and (fp32) the item sums,
         // after the mesh stacks (none for sphere scenes), then the CohConst block
         constexpr size_t WB =
-            coh_wave_bytes(MESH, (TRAV & TRAV_NOSUM) == 0, coh_fifo_entries(TRAV), EXACT, coh_parks(MESH, TRAV, EXACT));
+            coh_wave_bytes(MESH, (TRAV & TRAV_NOSUM) == 0, coh_fifo_entries(TRAV), EXACT, coh_parks(MESH, TRAV, EXACT),
+                           coh_cands(MESH, TRAV, EXACT));
         unsigned char* r0 = (unsigned char*)(s_mstack + (size_t)BLOCK * P.mstack);
         unsigned char* w = r0 + (size_t)(tid >> 6) * WB;
         const CohConst* kc = (const CohConst*)(r0 + (size_t)(BLOCK / 64) * WB);
