@@ -6,7 +6,8 @@
 //     reference's own recursion (camera_cpu.h:8-26), on the host in fp64 -- against
 //     HIPImpl::Camera::ray_color, the same ray traced by the device's fp64 kernel on the
 //     same global random stream: colours and stream positions must agree bit for bit;
-//   * rendering a world that holds the disk is refused (std::invalid_argument).
+//   * rendering a world that holds the disk is refused (std::invalid_argument);
+//   * the batched form of ray_color, rt_radiance_rays, on a handful of the caller's own rays.
 // Exit status 0 = pass.
 #include <cstdio>
 #include <stdexcept>
@@ -133,8 +134,50 @@ int main() {
     } catch (const std::invalid_argument&) {
         refused = true;
     }
-    const bool ok = bad == 0 && counted->tests > 0 && hits > 0 && disk_hit && refused;
-    std::printf("rays %d mismatched %d world.hit %ld counted_sphere tests %ld disk_hit %d render_refused %d %s\n", rays,
-                bad, hits, counted->tests, disk_hit, refused, ok ? "PASS" : "FAIL");
+    // rt_radiance_rays: ray_color for a batch of the caller's own rays, each on its own counter
+    // stream (pixel, sample) -- here five rays of an orthographic view looking down -z, which
+    // rt_camera cannot produce.  The buffers are rt_host_alloc memory, which the device reads
+    // and writes in place; rt_last_kernel_ms waits for the call.
+    bool batch_ok = false;
+    {
+        constexpr int NR = 5;
+        rt_ctx* q = rt_create(0, 0x5EED, RT_PREC_F64);
+        scene_builder sb;
+        world.flatten(sb);
+        int rc = q ? rt_upload_scene_ex(q, sb.spheres.data(), (int)sb.spheres.size(), sb.materials.data(),
+                                        (int)sb.materials.size(), sb.triangles.data(), (int)sb.triangles.size())
+                   : RT_ERR_HIP;
+        double* qrays = (double*)rt_host_alloc(NR * 7 * sizeof(double));
+        rt_path_key* qkeys = (rt_path_key*)rt_host_alloc(NR * sizeof(rt_path_key));
+        double* qrad = (double*)rt_host_alloc(NR * 3 * sizeof(double));
+        uint32_t* qseg = (uint32_t*)rt_host_alloc(NR * sizeof(uint32_t));
+        if (rc == RT_OK && qrays && qkeys && qrad && qseg) {
+            for (int k = 0; k < NR; ++k) {
+                const double ray7[7] = {-4.0 + 2.0 * k, 1.0, 8.0, 0.0, 0.0, -1.0, 0.5};
+                for (int a = 0; a < 7; ++a) qrays[k * 7 + a] = ray7[a];
+                qkeys[k] = rt_path_key{(uint32_t)k, 0u, 0u, 0u};
+            }
+            float ms = 0.f;
+            rc = rt_radiance_rays(q, qrays, NR, qkeys, 50, qrad, qseg, nullptr);
+            if (rc == RT_OK) rc = rt_last_kernel_ms(q, &ms);
+            batch_ok = rc == RT_OK;
+            for (int k = 0; k < NR && batch_ok; ++k) {
+                std::printf("radiance ray %d: %.17g %.17g %.17g (%u segments)\n", k, qrad[k * 3], qrad[k * 3 + 1],
+                            qrad[k * 3 + 2], qseg[k]);
+                for (int a = 0; a < 3; ++a) batch_ok = batch_ok && qrad[k * 3 + a] >= 0.0 && qrad[k * 3 + a] <= 1.0;
+                batch_ok = batch_ok && qseg[k] >= 1 && qseg[k] <= 50;
+            }
+        }
+        if (rc != RT_OK) std::printf("rt_radiance_rays: %s (%s)\n", rt_error_string(rc), q ? rt_last_error(q) : "no context");
+        rt_host_free(qrays);
+        rt_host_free(qkeys);
+        rt_host_free(qrad);
+        rt_host_free(qseg);
+        if (q) rt_destroy(q);
+    }
+    const bool ok = bad == 0 && counted->tests > 0 && hits > 0 && disk_hit && refused && batch_ok;
+    std::printf("rays %d mismatched %d world.hit %ld counted_sphere tests %ld disk_hit %d render_refused %d "
+                "radiance_batch %d %s\n",
+                rays, bad, hits, counted->tests, disk_hit, refused, batch_ok, ok ? "PASS" : "FAIL");
     return ok ? 0 : 1;
 }

@@ -451,7 +451,40 @@ int rt_trace_rays_from(rt_ctx* ctx, const void* rays, int num_rays, const int32_
  * caller built against 12 keeps working, and one that needs rt_occluded looks the symbol up. */
 int rt_occluded(rt_ctx* ctx, const void* rays, int num_rays, const void* intervals, uint8_t* occluded,
                 void* stream);
-/* The same, instrumented (fp32 sphere scenes; synchronous): counters = {node-loop wave
+/* Batched ray_color (camera_cpu.h:8-26) over caller-supplied rays: radiance[i] =
+ * ray_color(rays[i], max_depth, world), one value per ray.  Nothing is summed and nothing is
+ * rounded to the frame's fixed-point grid: the caller reduces.  A custom camera (orthographic,
+ * fisheye, a light probe, a sampler of the caller's own, a subset of pixels) is the caller's
+ * rays + the caller's (pixel, sample) keys + a sum.
+ * rays: as for rt_trace_rays.  keys: device memory, one rt_path_key per ray, or NULL for
+ * {i, 0, 0, 0} on ray i.  Ray i draws from the RT-CRNG-1 stream key(seed, pixel, sample)
+ * (oracle/rt_rng_spec.h rtspec_path_key, seed: rt_set_seed's), starting at draw number
+ * first_draw -- the draws a camera spent on the ray before ray_color, e.g. rt_camera's 2 for the
+ * pixel square, 2 per defocus-disk candidate and 1 for the time.  pad is ignored.  The key is the only per-ray
+ * state: two rays with equal key and equal values get equal results, and the output is the
+ * same bit for bit for any order, grid size or split of the batch.
+ * radiance: device memory, num_rays x 3 values of the context precision.  segments: NULL, or
+ * device memory for num_rays counts of that ray's world.hit calls (what rt_render's
+ * out_segments sums per pixel).  max_depth <= 0: every radiance and count is 0, no path is
+ * traced (camera_cpu.h:9-10).
+ * fp64 contexts return the reference's ray_color bit for bit: its sphere and triangle
+ * arithmetic, attenuations multiplied innermost-first (camera_cpu.h:19), no self-primitive
+ * rule; max_depth > 64 is RT_ERR_LIMIT as in rt_render_range.  fp32 contexts keep the fp32
+ * render kernels' arithmetic: the throughput is multiplied bounce by bounce, and every
+ * scattered segment treats the primitive it starts on as rt_trace_rays_from does; the caller's
+ * first segment names none (there are no origin ids here).
+ * Errors as rt_trace_rays (RT_ERR_NO_SCENE before an upload, RT_ERR_INVALID for num_rays < 0
+ * or a NULL rays / radiance with num_rays > 0, RT_ERR_LIMIT past 160 KiB of LDS); num_rays ==
+ * 0 is a no-op.  A non-finite ray component gives an unspecified value for that ray only; every
+ * path ends (at most max_depth segments).  Asynchronous on `stream` (NULL: the context's);
+ * rt_last_kernel_ms times it.  Calls on one context share a device counter: enqueue them on
+ * one stream, or order them.  Added to ABI 12 without a version bump, as rt_occluded was. */
+typedef struct {
+    uint32_t pixel, sample, first_draw, pad;
+} rt_path_key;
+int rt_radiance_rays(rt_ctx* ctx, const void* rays, int num_rays, const rt_path_key* keys, int max_depth,
+                     void* radiance, uint32_t* segments, void* stream);
+/* rt_trace_rays, instrumented (fp32 sphere scenes; synchronous): counters = {node-loop wave
  * iterations, their active lanes, sphere-loop wave iterations, their active lanes}. */
 int rt_trace_rays_diag(rt_ctx* ctx, const void* rays, int num_rays, rt_hit* hits, uint64_t counters[4]);
 

@@ -138,7 +138,13 @@ SIGNATURES = {
     "rt_trace_rays_from": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
     "rt_trace_rays_diag": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.POINTER(C.c_uint64)]),
     "rt_occluded": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),   # ABI 12
+    "rt_radiance_rays": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p,
+                                   C.c_void_p]),   # ABI 12
 }
+
+# rt_path_key (16 B): rt_radiance_rays' per-ray RNG stream (pixel, sample) and first draw number
+RtPathKey = np.dtype([("pixel", "<u4"), ("sample", "<u4"), ("first_draw", "<u4"), ("pad", "<u4")])
+assert RtPathKey.itemsize == 16
 
 # rt_hit (72 B): rt_trace_rays' per-ray hit record
 HIT_DTYPE = np.dtype([("t", "<f8"), ("p", "<f8", (3,)), ("normal", "<f8", (3,)), ("id", "<i4"),
@@ -509,6 +515,43 @@ class Renderer:
         if n and out.max() > 1:
             raise RtError(f"rt_occluded wrote byte {int(out.max())}")
         return out.astype(bool)
+
+    def radiance_rays(self, rays_dev: int, n: int, keys_dev: int | None, max_depth: int, out_dev: int,
+                      segments_dev: int | None = None, stream: int | None = None) -> None:
+        """rt_radiance_rays: ray_color of n rays (7 values each, device), ray i on the RNG stream of
+        keys[i] (RtPathKey records, device; a null pointer: {i, 0, 0}) -> n x 3 radiance values
+        (device) and, unless null, n uint32 segment counts (device)."""
+        self._check(self._L.rt_radiance_rays(self.ctx, C.c_void_p(rays_dev or 0), n, C.c_void_p(keys_dev or 0),
+                                             max_depth, C.c_void_p(out_dev or 0), C.c_void_p(segments_dev or 0),
+                                             C.c_void_p(stream or 0)), "rt_radiance_rays")
+
+    def radiance_rays_host(self, rays: np.ndarray, keys: np.ndarray | None = None, max_depth: int = 50,
+                           segments: bool = False):
+        """rt_radiance_rays through device copies: rays[n, 7] (context precision) and keys[n]
+        (RtPathKey; None: {i, 0, 0} for ray i) -> radiance[n, 3], or with segments=True
+        (radiance[n, 3], segments uint32[n])."""
+        import torch
+        # (writable copies where the caller's arrays are read-only: torch.from_numpy wants them so)
+        rays = np.require(rays, dtype=self.dtype, requirements=["C", "W"]).reshape(-1, 7)
+        n = len(rays)
+        d_rays = torch.from_numpy(rays if n else np.zeros((1, 7), self.dtype)).to("cuda")
+        d_keys = None
+        if keys is not None:
+            keys = np.require(keys, dtype=RtPathKey, requirements=["C", "W"]).reshape(-1)
+            if len(keys) != n:
+                raise ValueError(f"keys holds {len(keys)} records for {n} rays")
+            d_keys = torch.from_numpy((keys if n else np.zeros(1, RtPathKey)).view(np.uint8)).to("cuda")
+        d_out = torch.full((max(1, n), 3), float("nan"), dtype=torch.from_numpy(rays[:0]).dtype, device="cuda")
+        d_seg = torch.full((max(1, n),), -1, dtype=torch.int32, device="cuda") if segments else None
+        stream = torch.cuda.current_stream().cuda_stream
+        torch.cuda.synchronize()
+        self.radiance_rays(d_rays.data_ptr(), n, d_keys.data_ptr() if d_keys is not None else None, max_depth,
+                           d_out.data_ptr(), d_seg.data_ptr() if segments else None, stream)
+        torch.cuda.synchronize()
+        out = d_out.cpu().numpy()[:n]
+        if segments:
+            return out, d_seg.cpu().numpy()[:n].view(np.uint32)
+        return out
 
     def trace_rays_diag(self, rays_dev: int, n: int, hits_dev: int) -> dict:
         c = (C.c_uint64 * 4)()

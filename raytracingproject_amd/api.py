@@ -295,6 +295,17 @@ class camera:
             rtweekend.random_double()
         return col
 
+    def ray_colors(self, rays, depth: int, world: hittable, keys=None) -> np.ndarray:
+        """camera_cpu.h:8-26 for MANY rays on the GPU (rt_radiance_rays), the batched counterpart
+        of ray_color: rays[n, 7] (origin, direction, time) -> radiance[n, 3] in the camera's
+        precision.  Ray i draws from the counter stream of keys[i] (N.RtPathKey: pixel, sample,
+        first_draw; None: {i, 0, 0}) under the camera's seed; the global reference stream is not
+        touched.  Runs on the camera's own renderer, as render does."""
+        if self._renderer is None:
+            self._renderer = N.Renderer(self.device, self.seed, self.precision)
+        self._upload(self._renderer, world)
+        return self._renderer.radiance_rays_host(rays, keys, depth)
+
 
 def write_ppm(out, rgb: np.ndarray) -> None:
     """PPM P3 exactly as camera.h:35 and color.h:32-34 print it."""

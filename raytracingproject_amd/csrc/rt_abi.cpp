@@ -233,6 +233,7 @@ void rt_destroy(rt_ctx* c) {
     (void)hipFree(c->d_used);
     (void)hipFree(c->d_samples);
     (void)hipFree(c->d_queue64);
+    (void)hipFree(c->d_queue_rad);
     (void)hipFree(c->d_gather);
     for (auto& a : c->accum) {
         (void)hipFree(a.acc);
@@ -1035,6 +1036,40 @@ int rt_occluded(rt_ctx* c, const void* rays, int n, const void* intervals, uint8
     const hipError_t e = c->precision == RT_PREC_F64 ? launch_occluded_f64(P, lds, st, rays, n, intervals, occluded)
                                                      : launch_occluded_f32(P, lds, st, rays, n, intervals, occluded);
     if (e != hipSuccess) return fail(c, RT_ERR_HIP, "occlusion launch: %s", hipGetErrorString(e));
+    HIPCHK(c, hipEventRecord(c->ev1, st));
+    c->timed = true;
+    return RT_OK;
+}
+
+int rt_radiance_rays(rt_ctx* c, const void* rays, int n, const rt_path_key* keys, int max_depth, void* radiance,
+                     uint32_t* segments, void* stream) {
+    if (!c) return RT_ERR_INVALID;
+    if (!c->has_scene) return fail(c, RT_ERR_NO_SCENE, "rt_radiance_rays before rt_upload_scene");
+    if (n < 0 || (n > 0 && (!rays || !radiance)))
+        return fail(c, RT_ERR_INVALID, "rt_radiance_rays: %d rays, rays %p, radiance %p", n, rays, radiance);
+    if (c->precision == RT_PREC_F64 && max_depth > 64)
+        return fail(c, RT_ERR_LIMIT, "fp64 path keeps at most 64 bounces (max_depth %d)", max_depth);
+    RenderParams P;
+    size_t lds;
+    if (int rc = query_setup(c, "rt_radiance_rays", P, lds)) return rc;
+    if (n == 0) return RT_OK;
+    P.max_depth = max_depth;
+    if (!c->d_queue_rad) HIPCHK(c, hipMalloc((void**)&c->d_queue_rad, QUEUE_CTRL_BYTES));
+    P.queue = c->d_queue_rad;
+    hipStream_t st = stream ? (hipStream_t)stream : c->stream;
+    HIPCHK(c, hipEventRecord(c->ev0, st));
+    hipError_t e;
+    if (max_depth <= 0) {   // camera_cpu.h:9-10: no path, no light (all-zero bits are 0 in either precision)
+        e = hipMemsetAsync(radiance, 0, (size_t)n * 3 * elem_bytes(c), st);
+        if (e == hipSuccess && segments) e = hipMemsetAsync(segments, 0, (size_t)n * sizeof(uint32_t), st);
+    } else {
+        e = hipMemsetAsync(c->d_queue_rad, 0, QUEUE_CTRL_BYTES, st);
+        if (e == hipSuccess)
+            e = c->precision == RT_PREC_F64
+                    ? launch_radiance_f64(P, lds, st, rays, n, keys, radiance, segments, c->n_cu)
+                    : launch_radiance_f32(P, lds, st, rays, n, keys, radiance, segments, c->n_cu);
+    }
+    if (e != hipSuccess) return fail(c, RT_ERR_HIP, "radiance launch: %s", hipGetErrorString(e));
     HIPCHK(c, hipEventRecord(c->ev1, st));
     c->timed = true;
     return RT_OK;

@@ -79,6 +79,7 @@ struct rt_ctx {
     int* d_used = nullptr;
     void* d_samples = nullptr;  // per-sample radiance of chunked launches
     uint32_t* d_queue64 = nullptr;   // fp64 persistent lanes (f64_kernel 3): work-queue control block
+    uint32_t* d_queue_rad = nullptr;   // rt_radiance_rays: the launch's per-XCD heads (a control block of its own)
     size_t samples_cap = 0;
     void* d_gather = nullptr;   // rt_render_frame_multi: all contexts' shards
     size_t gather_cap = 0;

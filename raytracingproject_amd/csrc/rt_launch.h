@@ -47,6 +47,15 @@ hipError_t launch_occluded_f32(const RenderParams& P, size_t lds_bytes, hipStrea
                                const void* intervals, uint8_t* occluded);
 hipError_t launch_occluded_f64(const RenderParams& P, size_t lds_bytes, hipStream_t stream, const void* rays, int n,
                                const void* intervals, uint8_t* occluded);
+// batched ray_color (rt_radiance_rays): n rays as above, keys: null ({i, 0, 0} for ray i) or n
+// rt_path_key -> n x 3 radiance values of the context precision and (segments: may be null) n
+// closest-hit counts.  Persistent lanes that claim ray indices from the per-XCD heads of P.queue
+// (QUEUE_CTRL_BYTES, zeroed on the stream by the caller); P.max_depth >= 1; n_cu: the device's compute units (<= 0: unknown),
+// which with the kernel's registers and lds_bytes bound the grid to what stays resident.
+hipError_t launch_radiance_f32(const RenderParams& P, size_t lds_bytes, hipStream_t stream, const void* rays, int n,
+                               const void* keys, void* radiance, uint32_t* segments, int n_cu);
+hipError_t launch_radiance_f64(const RenderParams& P, size_t lds_bytes, hipStream_t stream, const void* rays, int n,
+                               const void* keys, void* radiance, uint32_t* segments, int n_cu);
 hipError_t launch_tape_f64(const RenderParams& P, int max_depth, const double* ray7, const double* tape, int tape_len,
                            double* out, int* used, hipStream_t stream);
 // element: 4 (float/uint32) or 8 (double); channels: 1 or 3

@@ -5,6 +5,7 @@
 #include <algorithm>
 
 #include "rt_occluded.h"   // (includes rt_render_impl.h)
+#include "rt_radiance.h"
 
 namespace rtx {
 
@@ -132,6 +133,34 @@ hipError_t launch_occluded_f32(const RenderParams& P, size_t lds_bytes, hipStrea
     else
         hipLaunchKernelGGL((occluded_kernel<float, false, B, TS, false>), dim3(grid), dim3(B), lds_bytes, stream, P, r,
                            n, iv, occluded);
+    return hipGetLastError();
+}
+
+// Batched ray_color (rt_radiance_rays), fp32: launch_trace_f32's traversal flags, so that a
+// ray's first segment is the closest-hit query's.  Register budgets: 8 waves per SIMD (<= 64
+// VGPRs) for spheres, the sphere render kernels' -- the bounce loop without a camera and without
+// sums takes 54 and spills nothing, so a small scene's LDS copy leaves the full 8 waves -- and
+// the mesh render kernels' 6 (<= 80 VGPRs; 76, no spill) for meshes.
+constexpr int RADIANCE_WPE = 8, RADIANCE_MESH_WPE = 6;
+hipError_t launch_radiance_f32(const RenderParams& P, size_t lds_bytes, hipStream_t stream, const void* rays, int n,
+                               const void* keys, void* radiance, uint32_t* segments, int n_cu) {
+    if (n <= 0) return hipSuccess;
+    constexpr int B = TRACE_BLOCK;
+    constexpr int TS = TRAV_SELROOT | TRAV_B128 | TRAV_CULL, TM = TRAV_SELROOT | TRAV_CULL | TRAV_MIFIF;
+    const float* r = (const float*)rays;
+    const PathKey* k = (const PathKey*)keys;
+    float* o = (float*)radiance;
+    if (P.n_mnodes > 0) {
+        auto* kern = radiance_kernel<float, false, B, RADIANCE_MESH_WPE, TM, true>;
+        static const int v = radiance_vgprs((const void*)kern);
+        hipLaunchKernelGGL(kern, dim3(radiance_grid<B>(v, lds_bytes, n, n_cu)), dim3(B), lds_bytes, stream, P, r, n,
+                           k, o, segments);
+    } else {
+        auto* kern = radiance_kernel<float, false, B, RADIANCE_WPE, TS, false>;
+        static const int v = radiance_vgprs((const void*)kern);
+        hipLaunchKernelGGL(kern, dim3(radiance_grid<B>(v, lds_bytes, n, n_cu)), dim3(B), lds_bytes, stream, P, r, n,
+                           k, o, segments);
+    }
     return hipGetLastError();
 }
 

@@ -2,6 +2,7 @@
 // operation rounds as in the g++ build of the reference.  Also hosts the small
 // precision-agnostic kernels (unshard, quantize).
 #include "rt_occluded.h"   // (includes rt_render_impl.h)
+#include "rt_radiance.h"
 
 namespace rtx {
 
@@ -259,6 +260,30 @@ hipError_t launch_occluded_f64(const RenderParams& P, size_t lds_bytes, hipStrea
     else
         hipLaunchKernelGGL((occluded_kernel<double, true, B, TRAV_F32BOX, false>), dim3(grid), dim3(B), lds_bytes,
                            stream, P, r, n, iv, occluded);
+    return hipGetLastError();
+}
+
+// Batched ray_color (rt_radiance_rays), fp64: the reference's arithmetic with the default fp64
+// kernel's box tests (conservative fp32 slabs, which only prune), at the fp64 render kernels'
+// register budget (4 waves per SIMD, <= 128 VGPRs).
+hipError_t launch_radiance_f64(const RenderParams& P, size_t lds_bytes, hipStream_t stream, const void* rays, int n,
+                               const void* keys, void* radiance, uint32_t* segments, int n_cu) {
+    if (n <= 0) return hipSuccess;
+    constexpr int B = TRACE_BLOCK;
+    const double* r = (const double*)rays;
+    const PathKey* k = (const PathKey*)keys;
+    double* o = (double*)radiance;
+    if (P.n_mnodes > 0) {
+        auto* kern = radiance_kernel<double, true, B, 4, TRAV_F32BOX, true>;
+        static const int v = radiance_vgprs((const void*)kern);
+        hipLaunchKernelGGL(kern, dim3(radiance_grid<B>(v, lds_bytes, n, n_cu)), dim3(B), lds_bytes, stream, P, r, n,
+                           k, o, segments);
+    } else {
+        auto* kern = radiance_kernel<double, true, B, 4, TRAV_F32BOX, false>;
+        static const int v = radiance_vgprs((const void*)kern);
+        hipLaunchKernelGGL(kern, dim3(radiance_grid<B>(v, lds_bytes, n, n_cu)), dim3(B), lds_bytes, stream, P, r, n,
+                           k, o, segments);
+    }
     return hipGetLastError();
 }
 
