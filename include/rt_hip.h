@@ -513,9 +513,14 @@ int rt_render_diag(rt_ctx* ctx, const rt_camera* cam, int samples_per_pixel, int
  * flushed straight to HBM (their item was no longer the wave's current one, or a value
  * outside [0, 1]), 26 item flushes (per pixel); mesh scenes add 27-30: 27 mesh-BVH node
  * wave iterations, 28 their active lanes, 29 triangle-test wave iterations, 30 their active
- * lanes.  31: grid walks suspended (the sphere-only kernel over the flat grid walk, see
- * RT_GRID_SUSPEND in INTEGRATION.md; 0 for every other kernel); a resumed walk counts no new
- * world.hit call in slot 10, though its trace counts in slots 0 and 1. */
+ * lanes.  The fp32 sphere-only kernels over the sphere grid, which have no mesh loops, fill
+ * 27-29 with the primary-hit hand-over instead: 27 pop passes (shade rounds of a wave in which
+ * at least one lane popped a FIFO entry), 28 the lanes that popped in them (equal to slot 15),
+ * 29 primary hits adopted (kept by the waiting lane that traced them in the batch, see
+ * RT_BATCH_ADOPT in INTEGRATION.md; never queued, so not in slot 15).  31: grid walks
+ * suspended (the sphere-only kernel over the flat grid walk, see RT_GRID_SUSPEND in
+ * INTEGRATION.md; 0 for every other kernel); a resumed walk counts no new world.hit call in
+ * slot 10, though its trace counts in slots 0 and 1. */
 enum { RT_DIAG_SLOTS = 32 };
 int rt_render_diag_ex(rt_ctx* ctx, const rt_camera* cam, int samples_per_pixel, int max_depth, uint64_t* counters,
                       int n);

@@ -450,7 +450,16 @@ class Renderer:
                  "mnode_it", "mnode_act", "mtri_it", "mtri_act",
                  # resumable flat grid walks (RT_GRID_SUSPEND): suspended walks
                  "grid_suspensions"]
-        return {n: int(c[k]) for k, n in enumerate(names)}
+        d = {n: int(c[k]) for k, n in enumerate(names)}
+        # slots 27-29 in the fp32 sphere-only grid kernels (no mesh loops there): shade rounds in
+        # which a lane popped a FIFO entry, the lanes that popped in them (= x15), and the primary
+        # hits a waiting lane kept from its own batch ray (RT_BATCH_ADOPT).  Every other kernel
+        # (sphere tree, mesh and mixed scenes, where these slots count the mesh loops): None
+        i = self.scene_info()
+        grid = self.precision == RT_PREC_F32 and i.num_triangles == 0 and bool(i.render_traversal & RT_TRAV_GRID)
+        d.update(pop_passes=d["mnode_it"] if grid else None, pop_lanes=d["mnode_act"] if grid else None,
+                 hits_adopted=d["mtri_it"] if grid else None)
+        return d
 
     def trace_rays(self, rays_dev: int, n: int, hits_dev: int, stream: int | None = None) -> None:
         """rt_trace_rays: n rays (7 values each, device) -> n rt_hit records (device)."""

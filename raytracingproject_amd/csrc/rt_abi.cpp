@@ -188,6 +188,16 @@ static bool parse_batch_cull(const char* s, int& cap) {
     return false;
 }
 
+// RT_BATCH_ADOPT: "1" (a lane waiting for a path keeps the hit of its own camera ray in a
+// batch; the default, also unset or empty) or "0" (every primary hit goes through the FIFO,
+// the kernel of before).  No rt_tuning field either: the frame does not depend on it.
+static bool parse_batch_adopt(const char* s, int& on) {
+    if (!s || !*s) return true;
+    if ((s[0] != '0' && s[0] != '1') || s[1]) return false;
+    on = s[0] - '0';
+    return true;
+}
+
 rt_ctx* rt_create(int device, uint64_t seed, int precision) {
     if (precision != RT_PREC_F32 && precision != RT_PREC_F64) return nullptr;
     int n = 0;
@@ -201,6 +211,11 @@ rt_ctx* rt_create(int device, uint64_t seed, int precision) {
     }
     if (!parse_batch_cull(getenv("RT_BATCH_CULL"), c->batch_cap)) {
         fprintf(stderr, "rt_create: RT_BATCH_CULL must be 0..%d\n", BATCH_CAND_CAP);
+        delete c;
+        return nullptr;
+    }
+    if (!parse_batch_adopt(getenv("RT_BATCH_ADOPT"), c->batch_adopt)) {
+        fprintf(stderr, "rt_create: RT_BATCH_ADOPT must be 0 or 1\n");
         delete c;
         return nullptr;
     }
@@ -662,7 +677,7 @@ static int render_range_f32(rt_ctx* c, const LaunchPlan& plan, RenderParams P, s
     P.gsus_lanes = c->gsus_lanes;
     P.gsus_iters = c->gsus_iters;
     P.batch_cap = c->batch_cap;
-    P.batch_pad = 0;
+    P.batch_adopt = c->batch_adopt;
     if (!slot->queue) HIPCHK(c, hipMalloc((void**)&slot->queue, QUEUE_CTRL_BYTES));
     P.queue = slot->queue;
     {

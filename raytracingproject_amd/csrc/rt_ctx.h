@@ -52,6 +52,9 @@ struct rt_ctx {
     // r09: per-item candidate lists (RenderParams::batch_cap), from the environment's
     // RT_BATCH_CULL at rt_create
     int batch_cap = BATCH_CAND_CAP;
+    // r10: waiting lanes adopt their own batch hits (RenderParams::batch_adopt), from the
+    // environment's RT_BATCH_ADOPT at rt_create
+    int batch_adopt = 1;
     int* d_remap = nullptr;     // rt_trace_rays: kernel id slot -> input index (spheres | big | triangles)
     int* d_unmap = nullptr;     // rt_trace_rays_from: input index -> Hit::id (d_remap's inverse), n_unmap entries
     int n_unmap = 0;

@@ -211,7 +211,10 @@ struct RenderParams {
     // the environment's RT_BATCH_CULL at rt_create): an item whose tile's camera rays can reach
     // at most batch_cap spheres (rt_batch_cull.h) tests those instead of walking the grid;
     // 0: never (every batch walks), at most BATCH_CAND_CAP
-    int batch_cap, batch_pad;
+    // batch_adopt (r10, the same kernels; the environment's RT_BATCH_ADOPT at rt_create): 1: a
+    // lane waiting for a path keeps the hit of the camera ray it traced in the batch instead of
+    // queueing it (coh_adopts); 0: every primary hit goes through the FIFO
+    int batch_cap, batch_adopt;
 };
 // (the defaults: profiles/r07/cpu/grid_resume_bound_r07.txt, then measured: DESIGN.md §5 r07)
 constexpr int GSUS_DEFAULT_LANES = 16, GSUS_DEFAULT_ITERS = 8;
@@ -632,6 +635,11 @@ constexpr bool coh_parks(bool mesh, int tr, bool f64) { return mesh && !f64 && (
 // the current item's camera rays can reach (BATCH_CAND_BYTES; rt_batch_cull.h).  The tree
 // kernels, at 79.6 of the 80 KB that let two workgroups share a CU, have no room for it.
 constexpr bool coh_cands(bool mesh, int tr, bool f64) { return !mesh && !f64 && (tr & TRAV_GRID) != 0; }
+// r10: in the same kernels a lane that waits for a path while the wave traces a batch adopts
+// the hit of its own camera ray (ray, RNG state and hit are in its registers) instead of
+// pushing it to the FIFO for some lane to pop and regenerate (render_coherent's batch).  The
+// tree, mixed, mesh and fp64 kernels sit at their register limits and keep the FIFO for every hit.
+constexpr bool coh_adopts(bool mesh, int tr, bool f64) { return coh_cands(mesh, tr, f64); }
 // LDS views by 32-bit LDS byte address (the sphere grid's flat walk and record reads)
 typedef __attribute__((address_space(3))) const uint32_t lds_cu32;
 typedef __attribute__((address_space(3))) const float4 lds_cf4;

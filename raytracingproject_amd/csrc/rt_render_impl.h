@@ -407,10 +407,14 @@ __device__ __forceinline__ void flush_sample(const RenderParams& P, uint32_t pix
 // the same nodes in the same order.  So camera rays are traced apart from the rest:
 //   * batch: the wave traces sample s of all 64 pixels of its current work item (tile,
 //     samples [s0, s0 + c)) -- one coherent wave of camera rays.  Misses (the sky) are
-//     finished on the spot; hits go to the wave's FIFO of primary hits in LDS;
-//   * bounce loop: a lane whose path ended pops the next primary hit and regenerates its
-//     camera ray (same RNG stream); then ONE shade pass serves popped primaries and
-//     scattered rays alike, so the wave shades once per bounce instead of twice.  Batches
+//     finished on the spot; hits go to the wave's FIFO of primary hits in LDS -- except,
+//     in the fp32 sphere-grid kernels (coh_adopts, r10), the hit of a lane that is itself
+//     waiting for a path: that lane keeps ray, RNG state and hit and shades them next;
+//   * bounce loop: a lane whose path ended (and that adopted nothing in a batch) pops the
+//     next primary hit and regenerates its camera ray (same RNG stream); then ONE shade
+//     pass serves adopted and popped primaries and scattered rays alike, so the wave
+//     shades once per bounce instead of twice; when every waiting lane adopted, the pop
+//     is skipped by the whole wave.  Batches
 //     run when the FIFO holds fewer hits than lanes waiting; lanes are refilled until
 //     fewer than coh_refill of them idle.  Only scattered rays are traced in the bounce
 //     loop.
@@ -526,7 +530,56 @@ __device__ __forceinline__ void render_coherent(const RenderParams& P0, const Sc
         if (DIAG) ++n_paths;
     };
 
-    auto batch = [&]() {
+    // this lane's path
+    bool live = false, ready = false, fin = false;   // holds a path; holds a hit to shade; no work left
+    // r07: the bounce trace of the sphere-only flat grid walk may suspend a lane's walk
+    // (closest_hit SUSP).  Such a lane stays live and not ready: it shades nothing, pops
+    // nothing, does not count as idle, keeps its ray, self, pix, rng, elig and scatter count,
+    // and the next trace resumes its walk from tres with the closest hit so far in h.
+    constexpr bool SUSP = !EXACT && !MESH && (TR & TRAV_GRID) != 0 && (TR & TRAV_GFLAT) != 0;
+    [[maybe_unused]] float tres = -1.f;              // >= 0: the suspended walk's resume distance
+    [[maybe_unused]] unsigned long long n_susp = 0;  // DIAG: suspensions
+    uint32_t pix = 0;
+    uint32_t psid = 0;   // EXACT: the path's sample - sample_begin
+    V3<R> thr = mk((R)1, (R)1, (R)1);
+    [[maybe_unused]] V3<R> att_stack[EXACT ? 64 : 1];   // EXACT: the path's attenuations (scratch)
+    CounterRng rng;
+    rng.st = 0;
+    int nsc = 0, self = NO_SELF;
+    // coh_parks: the throughput and scatter count live in LDS (COH_PARK_BYTES, lane-strided),
+    // touched only where a hit is shaded or a path ends instead of held across the trace
+    constexpr bool PARK = coh_parks(MESH, TRAV, EXACT);
+    [[maybe_unused]] float* const park =
+        (float*)((unsigned char*)fifo + (size_t)FIFO * sizeof(CohEntryX<R, MESH>) + (SUMS ? COH_SUM_BYTES : 0)) + lane;
+    auto park_thr = [&]() -> V3<R> { return mk((R)park[0], (R)park[64], (R)park[128]); };
+    auto park_nsc = [&]() -> int { return __float_as_int(park[192]); };
+    auto park_set = [&](V3<R> t, int n) {
+        park[0] = (float)t.x;
+        park[64] = (float)t.y;
+        park[128] = (float)t.z;
+        park[192] = __int_as_float(n);
+    };
+    Ray<R> ray;
+    ray.o = ray.d = thr;
+    ray.time = (R)0;
+    Hit<R> h;
+    h.t = (R)0;
+    h.td = 0.0;
+    h.id = -1;
+
+    // r10 (coh_adopts): a batch runs because lanes wait for a path, and each of them traces a
+    // camera ray of its own in it.  Such a lane whose ray hit keeps the path: the batch's ray,
+    // RNG state and hit are what the pop of that FIFO entry would rebuild, value for value --
+    // the ray by the same operations on the same draws, the RNG state because batch and pop
+    // consume the same draws (the defocus disk's rejected candidates are drawn here and
+    // skipped there, kd == 15 drawn again: the state after is the same), the hit from the
+    // entry's fields.  Only the other hits are queued.  Which lane shades a path never changes
+    // a bit of the frame (above), so it stays what it was.  need: the caller's !fin && !live.
+    constexpr bool ADOPT = coh_adopts(MESH, TRAV, EXACT);
+    // (the adoption sets thr and nsc in registers and no psid: not the parked state, not EXACT)
+    static_assert(!ADOPT || (!PARK && !EXACT), "adopted hits: the fp32 sphere-only grid kernels");
+    [[maybe_unused]] unsigned long long n_adopt = 0, n_pop_pass = 0, n_pop_lanes = 0;   // DIAG
+    auto batch = [&]([[maybe_unused]] const bool need) {
         const unsigned long long tb = DIAG ? __builtin_amdgcn_s_memtime() : 0;
         if (bi >= cur.c) {
             if (SUMS && cur.lt >= 0) {   // the item's pixel sums to HBM: lane q has pixel q
@@ -575,6 +628,7 @@ __device__ __forceinline__ void render_coherent(const RenderParams& P0, const Sc
         const int px = cur.tx0 + (lane & 7), py = cur.ty0 + (lane >> 3);
         const uint32_t pp = (uint32_t)cur.lt * 64u + (uint32_t)lane;
         bool hit = false;
+        [[maybe_unused]] bool adopt = false;
         Hit<R> hb;
         hb.t = (R)0;
         hb.id = -1;
@@ -598,12 +652,32 @@ __device__ __forceinline__ void render_coherent(const RenderParams& P0, const Sc
                 finish(pp, true, sky(pr.d), 1u, (uint32_t)(s - P.sample_begin));
             } else {
                 hit = true;
+                if constexpr (ADOPT) {
+                    // (after the item switch's elig = false above: the item is the wave's
+                    // current one, s one of its samples)
+                    if (need && P.batch_adopt) {
+                        adopt = true;
+                        ray = pr;
+                        rng = r2;
+                        h.t = hb.t;
+                        h.td = (double)hb.t;
+                        h.id = hb.id;
+                        pix = pp;
+                        thr = mk((R)1, (R)1, (R)1);
+                        nsc = 0;
+                        self = NO_SELF;
+                        live = ready = true;
+                        elig = true;
+                        if (DIAG) ++n_adopt;
+                    }
+                }
             }
         } else if constexpr (EXACT) {   // no path (outside the image, depth 0): the sample is 0
             finish(pp, true, mk((R)0, (R)0, (R)0), 0u, (uint32_t)(s - P.sample_begin));
         }
-        const unsigned long long hm = __ballot(hit);
-        if (hit) {
+        const bool push = ADOPT ? hit && !adopt : hit;   // the hits no lane kept
+        const unsigned long long hm = __ballot(push);
+        if (push) {
             const uint32_t r = __builtin_amdgcn_mbcnt_hi((uint32_t)(hm >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)hm, 0u));
             CohEntryX<R, MESH> e;
             e.t = hb.t;
@@ -625,42 +699,6 @@ __device__ __forceinline__ void render_coherent(const RenderParams& P0, const Sc
         }
     };
 
-    // this lane's path
-    bool live = false, ready = false, fin = false;   // holds a path; holds a hit to shade; no work left
-    // r07: the bounce trace of the sphere-only flat grid walk may suspend a lane's walk
-    // (closest_hit SUSP).  Such a lane stays live and not ready: it shades nothing, pops
-    // nothing, does not count as idle, keeps its ray, self, pix, rng, elig and scatter count,
-    // and the next trace resumes its walk from tres with the closest hit so far in h.
-    constexpr bool SUSP = !EXACT && !MESH && (TR & TRAV_GRID) != 0 && (TR & TRAV_GFLAT) != 0;
-    [[maybe_unused]] float tres = -1.f;              // >= 0: the suspended walk's resume distance
-    [[maybe_unused]] unsigned long long n_susp = 0;  // DIAG: suspensions
-    uint32_t pix = 0;
-    uint32_t psid = 0;   // EXACT: the path's sample - sample_begin
-    V3<R> thr = mk((R)1, (R)1, (R)1);
-    [[maybe_unused]] V3<R> att_stack[EXACT ? 64 : 1];   // EXACT: the path's attenuations (scratch)
-    CounterRng rng;
-    rng.st = 0;
-    int nsc = 0, self = NO_SELF;
-    // coh_parks: the throughput and scatter count live in LDS (COH_PARK_BYTES, lane-strided),
-    // touched only where a hit is shaded or a path ends instead of held across the trace
-    constexpr bool PARK = coh_parks(MESH, TRAV, EXACT);
-    [[maybe_unused]] float* const park =
-        (float*)((unsigned char*)fifo + (size_t)FIFO * sizeof(CohEntryX<R, MESH>) + (SUMS ? COH_SUM_BYTES : 0)) + lane;
-    auto park_thr = [&]() -> V3<R> { return mk((R)park[0], (R)park[64], (R)park[128]); };
-    auto park_nsc = [&]() -> int { return __float_as_int(park[192]); };
-    auto park_set = [&](V3<R> t, int n) {
-        park[0] = (float)t.x;
-        park[64] = (float)t.y;
-        park[128] = (float)t.z;
-        park[192] = __int_as_float(n);
-    };
-    Ray<R> ray;
-    ray.o = ray.d = thr;
-    ray.time = (R)0;
-    Hit<R> h;
-    h.t = (R)0;
-    h.td = 0.0;
-    h.id = -1;
     // radiance of a path that left the scene (camera_cpu.h:19-25): EXACT multiplies the
     // attenuations innermost-first, as the reference recursion associates them
     auto sky_L = [&]() -> V3<R> {
@@ -701,7 +739,7 @@ __device__ __forceinline__ void render_coherent(const RenderParams& P0, const Sc
                 // (always, at 128 entries: count < k <= 64); otherwise the hits already
                 // there are popped first and the lanes still waiting batch next time round
                 if (count < k && !dry && count + 64u <= (uint32_t)FIFO) {
-                    batch();
+                    batch(need);
                     continue;
                 }
                 if (need) {
@@ -745,6 +783,10 @@ __device__ __forceinline__ void render_coherent(const RenderParams& P0, const Sc
                     }
                 }
                 const uint32_t took = k < count ? k : count;
+                if constexpr (DIAG && ADOPT) {   // (wave-uniform) passes in which a lane popped, their lanes
+                    n_pop_pass += took ? 1u : 0u;
+                    n_pop_lanes += took;
+                }
                 head += took;
                 count -= took;
             }
@@ -827,6 +869,11 @@ __device__ __forceinline__ void render_coherent(const RenderParams& P0, const Sc
         if (n_direct) atomicAdd(P.diag + 25, n_direct);
         if (n_item_flush) atomicAdd(P.diag + 26, n_item_flush);
         if (n_susp) atomicAdd(P.diag + 31, n_susp);
+        if constexpr (ADOPT) {   // slots 27-29, the mesh loops' in mesh scenes: pop passes, adopted hits
+            if (l0 && n_pop_pass) atomicAdd(P.diag + 27, n_pop_pass);
+            if (l0 && n_pop_lanes) atomicAdd(P.diag + 28, n_pop_lanes);
+            if (n_adopt) atomicAdd(P.diag + 29, n_adopt);
+        }
         if constexpr (MESH) {   // mesh BVH loops (batches and bounces together)
             const unsigned long long mv[4] = {dg.mnode_it + dgb.mnode_it, dg.mnode_act + dgb.mnode_act,
                                               dg.mtri_it + dgb.mtri_it, dg.mtri_act + dgb.mtri_act};

@@ -108,6 +108,15 @@ def main():
                 "drain_bounce_iters_per_wave": d["drain_bounce_it"] / d["waves"],
                 "bounce_iters_per_wave": d["bounce_it"] / d["waves"],
             }
+        if not mesh and info.render_traversal & N.RT_TRAV_GRID:
+            # sphere-only grid kernels (slots 27-29): how primary hits reach a shading lane
+            out["hand_over"] = {
+                "pop_passes": d["pop_passes"], "lanes_per_pop_pass": q(d["pop_lanes"], d["pop_passes"]),
+                "pop_passes_per_bounce_iter": q(d["pop_passes"], d["bounce_it"]),
+                "hits_popped": d["x15"], "hits_adopted": d["hits_adopted"],
+                "adopted_share": q(d["hits_adopted"], d["hits_adopted"] + d["x15"]),
+                "batches_per_bounce_iter": q(d["k_it1"], d["bounce_it"]),
+            }
         if mesh:
             traced = rays + d["segments"]   # camera rays (batches) + scattered rays
             out["mesh"] = {
