@@ -7,10 +7,12 @@
 //     HIPImpl::Camera::ray_color, the same ray traced by the device's fp64 kernel on the
 //     same global random stream: colours and stream positions must agree bit for bit;
 //   * rendering a world that holds the disk is refused (std::invalid_argument);
-//   * the batched form of ray_color, rt_radiance_rays, on a handful of the caller's own rays.
+//   * the batched form of ray_color, rt_radiance_rays, on a handful of the caller's own rays;
+//   * a crop window rendered through rt_render_pixels, against the same pixels of rt_render_frame.
 // Exit status 0 = pass.
 #include <cstdio>
 #include <stdexcept>
+#include <vector>
 
 #include "bvh.h"
 #include "camera_hip.h"
@@ -138,7 +140,7 @@ int main() {
     // stream (pixel, sample) -- here five rays of an orthographic view looking down -z, which
     // rt_camera cannot produce.  The buffers are rt_host_alloc memory, which the device reads
     // and writes in place; rt_last_kernel_ms waits for the call.
-    bool batch_ok = false;
+    bool batch_ok = false, crop_ok = false;
     {
         constexpr int NR = 5;
         rt_ctx* q = rt_create(0, 0x5EED, RT_PREC_F64);
@@ -169,15 +171,51 @@ int main() {
             }
         }
         if (rc != RT_OK) std::printf("rt_radiance_rays: %s (%s)\n", rt_error_string(rc), q ? rt_last_error(q) : "no context");
+        // rt_render_pixels: a 16 x 8 crop window of the 64 x 36 frame at 4 samples per pixel, one
+        // job {pixel, first sample, count} per pixel -- the sums rt_render_frame gives those pixels,
+        // bit for bit, without rendering the other 2,176.
+        if (rc == RT_OK) {
+            constexpr int W = 64, SPP = 4, X0 = 24, Y0 = 14, CW = 16, CH = 8, NJ = CW * CH;
+            rt_camera_desc desc{};
+            desc.aspect_ratio = 16.0 / 9.0;
+            desc.image_width = W;
+            desc.vfov = 20;
+            const double from[3] = {13, 2, 3}, up[3] = {0, 1, 0};
+            for (int a = 0; a < 3; ++a) desc.lookfrom[a] = from[a], desc.lookat[a] = 0, desc.vup[a] = up[a];
+            desc.defocus_angle = 0.6;
+            desc.focus_dist = 10.0;
+            rt_camera view;
+            rc = rt_camera_initialize(&desc, &view);
+            rt_pixel_job* jobs = (rt_pixel_job*)rt_host_alloc(NJ * sizeof(rt_pixel_job));
+            double* crop = (double*)rt_host_alloc(NJ * 3 * sizeof(double));
+            std::vector<double> frame(rc == RT_OK ? (size_t)W * view.image_height * 3 : 0);
+            if (rc == RT_OK && jobs && crop) {
+                for (int k = 0; k < NJ; ++k)
+                    jobs[k] = rt_pixel_job{(uint32_t)((Y0 + k / CW) * W + X0 + k % CW), 0u, (uint32_t)SPP, 0u};
+                float ms = 0.f;
+                rc = rt_render_pixels(q, &view, jobs, NJ, 50, 0, crop, nullptr, nullptr);
+                if (rc == RT_OK) rc = rt_last_kernel_ms(q, &ms);   // (waits for the call)
+                if (rc == RT_OK) rc = rt_render_frame(q, &view, SPP, 50, frame.data(), nullptr, nullptr);
+                crop_ok = rc == RT_OK;
+                for (int k = 0; k < NJ && crop_ok; ++k)
+                    for (int a = 0; a < 3; ++a)
+                        crop_ok = crop_ok && crop[k * 3 + a] == frame[(size_t)jobs[k].pixel * 3 + a];
+                std::printf("crop window %dx%d at (%d,%d): %s rt_render_frame, first pixel %.17g %.17g %.17g\n", CW, CH, X0,
+                            Y0, crop_ok ? "equals" : "DIFFERS FROM", crop[0], crop[1], crop[2]);
+            }
+            if (rc != RT_OK) std::printf("rt_render_pixels: %s (%s)\n", rt_error_string(rc), rt_last_error(q));
+            rt_host_free(jobs);
+            rt_host_free(crop);
+        }
         rt_host_free(qrays);
         rt_host_free(qkeys);
         rt_host_free(qrad);
         rt_host_free(qseg);
         if (q) rt_destroy(q);
     }
-    const bool ok = bad == 0 && counted->tests > 0 && hits > 0 && disk_hit && refused && batch_ok;
+    const bool ok = bad == 0 && counted->tests > 0 && hits > 0 && disk_hit && refused && batch_ok && crop_ok;
     std::printf("rays %d mismatched %d world.hit %ld counted_sphere tests %ld disk_hit %d render_refused %d "
-                "radiance_batch %d %s\n",
-                rays, bad, hits, counted->tests, disk_hit, refused, batch_ok, ok ? "PASS" : "FAIL");
+                "radiance_batch %d crop_window %d %s\n",
+                rays, bad, hits, counted->tests, disk_hit, refused, batch_ok, crop_ok, ok ? "PASS" : "FAIL");
     return ok ? 0 : 1;
 }

@@ -484,6 +484,72 @@ typedef struct {
 } rt_path_key;
 int rt_radiance_rays(rt_ctx* ctx, const void* rays, int num_rays, const rt_path_key* keys, int max_depth,
                      void* radiance, uint32_t* segments, void* stream);
+/* Sparse rendering: the sums rt_render / rt_render_range write, for a device list of pixel
+ * sample jobs instead of a whole shard of tiles with one sample range -- adaptive sampling, crop
+ * windows, re-rendering a dirty region, sparse previews, per-pixel budgets.
+ * jobs: device memory, num_jobs records.  pixel = j * image_width + i (row j, column i: the key
+ * rt_render gives that pixel's RNG streams); the job's samples are [sample_begin, sample_begin +
+ * sample_count); pad is ignored.  Jobs are independent: a pixel may appear in several, with
+ * overlapping ranges.  A job with sample_count == 0 or pixel >= width * height contributes
+ * nothing -- its outputs are 0, or untouched when accumulate is 1 -- and is no error.  The flat
+ * sample list is job 0's samples in order, then job 1's, ...; T is the valid jobs' total count.
+ * out_sums: device memory, num_jobs x 3 values of the context precision; out_segments: NULL, or
+ * device memory for num_jobs world.hit counts of that job's samples.
+ * fp64 contexts: out = start + L(s0) + L(s0 + 1) + ..., sequential fp64 additions in sample
+ * order, start = 0.0 or (accumulate = 1) the value already in out_sums[job]; L is the
+ * reference's ray_color of get_ray(i, j) on the RT-CRNG-1 stream key(seed, pixel, sample).  A
+ * job {p, 0, spp} is rt_render's sum of pixel p bit for bit, and {p, 0, a} followed by {p, a, b}
+ * with accumulate equals {p, 0, a + b}.
+ * fp32 contexts: the fp32 render kernels' rule.  Each sample channel is rounded to
+ * rintf(L 2^19), the roundings are summed exactly as integers S, and out =
+ * (float)((double)(S 2^9) 2^-28) -- the same bits for any order or split; a non-finite or
+ * overflowing sample makes the channel NaN or +-inf as in rt_render.  accumulate = 1 starts from
+ * rint((double)out 2^28) (non-finite values as NaN / +-inf), which is what rt_render_range does
+ * for a buffer the context holds no sums for; the context's memory of rt_render_range's output
+ * buffers is neither used nor disturbed.  L is the fp32 render kernels' arithmetic (the camera
+ * vectors rounded once, the throughput multiplied bounce by bounce, the self-primitive rule on
+ * scattered segments only).  Out-of-range radiance aside, a job {p, s, n} is
+ * rt_render_range(s, n) at pixel p bit for bit.
+ * out_segments is overwritten, or added to with accumulate = 1.
+ * The tree is walked, never the sphere grid (as for every query).  fp64 passes: each sample is
+ * stored as a 28-byte record (3 doubles and one uint32) before the ordered reduction, and one
+ * pass holds floor(rt_tuning.sample_buffer_mb 2^20 / 28) samples of the flat list; a job that
+ * straddles a pass boundary continues in the next pass.
+ * Errors: RT_ERR_NO_SCENE before an upload; RT_ERR_INVALID for a bad camera, num_jobs < 0, or a
+ * NULL jobs / out_sums with num_jobs > 0; RT_ERR_LIMIT for fp64 max_depth > 64, past 160 KiB of
+ * LDS, or T > 2^31 - 1 (the scan is 64-bit).  num_jobs == 0 is a no-op.  max_depth <= 0: sums and
+ * counts are 0 (untouched with accumulate), no path kernel runs.
+ * T lives on the device and the host needs it to size the passes and check the limit: the call
+ * SYNCHRONISES on the stream once, after the scan of the jobs' counts, with an 8-byte copy;
+ * everything after that is asynchronous on `stream` (NULL: the context's).  rt_last_kernel_ms
+ * covers the whole call, scan included.  Calls on one context share device scratch: enqueue
+ * them on one stream, or order them.  Cost: one search of the job list per sample; in fp32 all
+ * samples of a job add to the same three words with atomics, and in fp64 one thread adds a job's
+ * samples in order, so split a job of 10^5 samples or more into several jobs of that pixel.
+ * Added to ABI 12 without a version bump, as rt_occluded. */
+typedef struct {
+    uint32_t pixel, sample_begin, sample_count, pad;
+} rt_pixel_job;
+int rt_render_pixels(rt_ctx* ctx, const rt_camera* cam, const rt_pixel_job* jobs, int num_jobs, int max_depth,
+                     int accumulate, void* out_sums, uint32_t* out_segments, void* stream);
+/* The camera's rays on the device: camera::get_ray (camera.h:87-113) for every sample of a job
+ * list (jobs, flat sample list and T as for rt_render_pixels).  For flat sample q: rays[q] = the
+ * ray, 7 values of the context precision {origin xyz, direction xyz, time}, in the render
+ * kernels' arithmetic of that precision; keys[q] = {pixel, sample, first_draw, 0} with
+ * first_draw the draws get_ray spent (2 for the pixel square, 2 per defocus-disk candidate
+ * including the accepted one when defocus_angle > 0, 1 for the time) -- ready for
+ * rt_radiance_rays, rt_trace_rays or rt_occluded; ray_job[q] = the job's index (ray_job may be
+ * NULL).  rt_radiance_rays(rays, keys), summed per job by rt_render_pixels' rules, equals
+ * rt_render_pixels.  Needs no scene: only the camera and the context's seed.
+ * rays, keys, ray_job: device memory for max_rays records.  *num_rays (host memory, may be NULL)
+ * receives T; T > max_rays is RT_ERR_INVALID with nothing written beyond *num_rays (call with
+ * max_rays = 0 to size the buffers).  Other errors: RT_ERR_INVALID for a bad camera, num_jobs <
+ * 0, or a NULL jobs / rays / keys with num_jobs > 0; RT_ERR_LIMIT for T > 2^31 - 1.  num_jobs ==
+ * 0 sets *num_rays = 0 and does nothing else.  Synchronises once after the scan, as
+ * rt_render_pixels; the rays are written asynchronously on `stream`; rt_last_kernel_ms covers
+ * the call. */
+int rt_camera_rays(rt_ctx* ctx, const rt_camera* cam, const rt_pixel_job* jobs, int num_jobs, void* rays,
+                   rt_path_key* keys, int32_t* ray_job, int64_t max_rays, int64_t* num_rays, void* stream);
 /* rt_trace_rays, instrumented (fp32 sphere scenes; synchronous): counters = {node-loop wave
  * iterations, their active lanes, sphere-loop wave iterations, their active lanes}. */
 int rt_trace_rays_diag(rt_ctx* ctx, const void* rays, int num_rays, rt_hit* hits, uint64_t counters[4]);

@@ -140,7 +140,15 @@ SIGNATURES = {
     "rt_occluded": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),   # ABI 12
     "rt_radiance_rays": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p,
                                    C.c_void_p]),   # ABI 12
+    "rt_render_pixels": (C.c_int, [C.c_void_p, C.POINTER(RtCamera), C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p,
+                                   C.c_void_p, C.c_void_p]),   # ABI 12
+    "rt_camera_rays": (C.c_int, [C.c_void_p, C.POINTER(RtCamera), C.c_void_p, C.c_int, C.c_void_p, C.c_void_p,
+                                 C.c_void_p, C.c_int64, C.POINTER(C.c_int64), C.c_void_p]),   # ABI 12
 }
+
+# rt_pixel_job (16 B): rt_render_pixels' / rt_camera_rays' job -- samples [sample_begin, +sample_count) of a pixel
+RtPixelJob = np.dtype([("pixel", "<u4"), ("sample_begin", "<u4"), ("sample_count", "<u4"), ("pad", "<u4")])
+assert RtPixelJob.itemsize == 16
 
 # rt_path_key (16 B): rt_radiance_rays' per-ray RNG stream (pixel, sample) and first draw number
 RtPathKey = np.dtype([("pixel", "<u4"), ("sample", "<u4"), ("first_draw", "<u4"), ("pad", "<u4")])
@@ -561,6 +569,86 @@ class Renderer:
         if segments:
             return out, d_seg.cpu().numpy()[:n].view(np.uint32)
         return out
+
+    def render_pixels(self, cam: RtCamera, jobs_dev: int, n: int, max_depth: int, out_dev: int,
+                      seg_dev: int | None = None, accumulate: bool = False, stream: int | None = None) -> None:
+        """rt_render_pixels: n jobs (RtPixelJob records, device) -> n x 3 sums of the context
+        precision (device) and, unless null, n uint32 segment counts (device); accumulate continues
+        what the outputs hold.  Synchronises once on the stream (the jobs' total count)."""
+        self._check(self._L.rt_render_pixels(self.ctx, C.byref(cam), C.c_void_p(jobs_dev or 0), n, max_depth,
+                                             1 if accumulate else 0, C.c_void_p(out_dev or 0),
+                                             C.c_void_p(seg_dev or 0), C.c_void_p(stream or 0)), "rt_render_pixels")
+
+    @staticmethod
+    def _jobs(jobs) -> np.ndarray:
+        return np.require(jobs, dtype=RtPixelJob, requirements=["C", "W"]).reshape(-1)
+
+    def render_pixels_host(self, cam: RtCamera, jobs: np.ndarray, max_depth: int = 50, segments: bool = False):
+        """rt_render_pixels through device copies: jobs (RtPixelJob[n]) -> sums[n, 3], or with
+        segments=True (sums[n, 3], segments uint32[n])."""
+        import torch
+        jobs = self._jobs(jobs)
+        n = len(jobs)
+        d_jobs = torch.from_numpy((jobs if n else np.zeros(1, RtPixelJob)).view(np.uint8)).to("cuda")
+        d_out = torch.full((max(1, n), 3), float("nan"), dtype=torch.from_numpy(np.zeros(0, self.dtype)).dtype,
+                           device="cuda")
+        d_seg = torch.full((max(1, n),), -1, dtype=torch.int32, device="cuda") if segments else None
+        stream = torch.cuda.current_stream().cuda_stream
+        torch.cuda.synchronize()
+        self.render_pixels(cam, d_jobs.data_ptr(), n, max_depth, d_out.data_ptr(),
+                           d_seg.data_ptr() if segments else None, False, stream)
+        torch.cuda.synchronize()
+        out = d_out.cpu().numpy()[:n]
+        if segments:
+            return out, d_seg.cpu().numpy()[:n].view(np.uint32)
+        return out
+
+    def camera_rays(self, cam: RtCamera, jobs_dev: int, n: int, rays_dev: int, keys_dev: int,
+                    ray_job_dev: int | None, max_rays: int, stream: int | None = None) -> int:
+        """rt_camera_rays: the camera's rays for every sample of n jobs (device) -> rays (7 values
+        each), keys (RtPathKey) and, unless null, the job index per ray, into device buffers of
+        max_rays records.  Returns the number of rays T; raises if T > max_rays (camera_rays_count
+        sizes the buffers)."""
+        t = C.c_int64(-1)
+        self._check(self._L.rt_camera_rays(self.ctx, C.byref(cam), C.c_void_p(jobs_dev or 0), n,
+                                           C.c_void_p(rays_dev or 0), C.c_void_p(keys_dev or 0),
+                                           C.c_void_p(ray_job_dev or 0), max_rays, C.byref(t),
+                                           C.c_void_p(stream or 0)), "rt_camera_rays")
+        return int(t.value)
+
+    def camera_rays_count(self, cam: RtCamera, jobs_dev: int, n: int, stream: int | None = None) -> int:
+        """The number of rays T rt_camera_rays would write for these jobs (a call with max_rays = 0,
+        whose RT_ERR_INVALID for T > 0 is the expected answer)."""
+        t = C.c_int64(-1)
+        one = C.c_void_p(jobs_dev or 0)   # (rays / keys: any non-null pointers; nothing is written)
+        rc = self._L.rt_camera_rays(self.ctx, C.byref(cam), one, n, one, one, None, 0, C.byref(t),
+                                    C.c_void_p(stream or 0))
+        if rc != RT_OK and not (rc == RT_ERR_INVALID and t.value > 0):
+            self._check(rc, "rt_camera_rays")
+        return int(t.value)
+
+    def camera_rays_host(self, cam: RtCamera, jobs: np.ndarray):
+        """rt_camera_rays through device copies: jobs (RtPixelJob[n]) -> (rays[T, 7] of the context
+        precision, keys RtPathKey[T], ray_job int32[T])."""
+        import torch
+        jobs = self._jobs(jobs)
+        n = len(jobs)
+        d_jobs = torch.from_numpy((jobs if n else np.zeros(1, RtPixelJob)).view(np.uint8)).to("cuda")
+        stream = torch.cuda.current_stream().cuda_stream
+        torch.cuda.synchronize()
+        t = self.camera_rays_count(cam, d_jobs.data_ptr(), n, stream)
+        d_rays = torch.full((max(1, t), 7), float("nan"), dtype=torch.from_numpy(np.zeros(0, self.dtype)).dtype,
+                            device="cuda")
+        d_keys = torch.zeros(max(1, t) * RtPathKey.itemsize, dtype=torch.uint8, device="cuda")
+        d_job = torch.full((max(1, t),), -1, dtype=torch.int32, device="cuda")
+        torch.cuda.synchronize()
+        got = self.camera_rays(cam, d_jobs.data_ptr(), n, d_rays.data_ptr(), d_keys.data_ptr(), d_job.data_ptr(), t,
+                               stream)
+        torch.cuda.synchronize()
+        if got != t:
+            raise RtError(f"rt_camera_rays counted {t} rays, then {got}")
+        return (d_rays.cpu().numpy()[:t], d_keys.cpu().numpy()[: t * RtPathKey.itemsize].view(RtPathKey),
+                d_job.cpu().numpy()[:t])
 
     def trace_rays_diag(self, rays_dev: int, n: int, hits_dev: int) -> dict:
         c = (C.c_uint64 * 4)()

@@ -306,6 +306,25 @@ class camera:
         self._upload(self._renderer, world)
         return self._renderer.radiance_rays_host(rays, keys, depth)
 
+    def render_pixels(self, world: hittable, pixels, sample_begin: int = 0, sample_count: int | None = None) -> np.ndarray:
+        """The sums camera::render accumulates (camera.h:40-44), for chosen pixels only
+        (rt_render_pixels): pixels[n, 2] of (i, j) = (column, row) -> sums[n, 3] in the camera's
+        precision, over samples [sample_begin, sample_begin + sample_count) of each (default
+        count: samples_per_pixel) -- the values render_arrays returns at those pixels, bit for bit.
+        A pixel outside the image gives 0.  Runs on the camera's own renderer, as render does."""
+        self.initialize()
+        if self._renderer is None:
+            self._renderer = N.Renderer(self.device, self.seed, self.precision)
+        self._upload(self._renderer, world)
+        ij = np.asarray(pixels, dtype=np.int64).reshape(-1, 2)
+        W, H = self._cam.image_width, self._cam.image_height
+        inside = (ij[:, 0] >= 0) & (ij[:, 0] < W) & (ij[:, 1] >= 0) & (ij[:, 1] < H)
+        jobs = np.zeros(len(ij), N.RtPixelJob)
+        jobs["pixel"] = np.where(inside, ij[:, 1] * W + ij[:, 0], 0xFFFFFFFF)
+        jobs["sample_begin"] = sample_begin
+        jobs["sample_count"] = self.samples_per_pixel if sample_count is None else sample_count
+        return self._renderer.render_pixels_host(self._cam, jobs, self.max_depth)
+
 
 def write_ppm(out, rgb: np.ndarray) -> None:
     """PPM P3 exactly as camera.h:35 and color.h:32-34 print it."""

@@ -87,22 +87,12 @@ int check_camera(rt_ctx* c, const rt_camera* cam) {
     return RT_OK;
 }
 
-void fill_params(const rt_ctx* c, const rt_camera* cam, int spp, int max_depth, int mesh_stack, RenderParams& P) {
-    std::memset(&P, 0, sizeof(P));
+// what camera_ray reads of the parameters: the image size, the seed and the camera's vectors
+// (rt_camera_rays needs no more, and no scene)
+void fill_camera(const rt_ctx* c, const rt_camera* cam, RenderParams& P) {
     P.W = cam->image_width;
     P.H = cam->image_height;
-    P.spp = spp;
-    P.max_depth = max_depth;
-    P.tiles_x = (P.W + 7) / 8;
-    P.tiles_x_inv = 1.0 / P.tiles_x;
-    P.tiles_x_inv_half = 0.5 * P.tiles_x_inv;
     P.seed32 = seed32_of(c->seed);
-    P.n_nodes = c->n_nodes;
-    P.n_spheres = c->n_sph;
-    P.n_mats = c->n_mat;
-    P.n_big = c->n_big;
-    P.n_front = c->n_front;
-    P.stack_size = stack_entries(c);
     P.defocus = cam->defocus_angle > 0;  // camera.h:94 tests defocus_angle <= 0
     for (int a = 0; a < 3; ++a) {
         P.f_center[a] = (float)cam->center[a];
@@ -118,6 +108,22 @@ void fill_params(const rt_ctx* c, const rt_camera* cam, int spp, int max_depth, 
         P.ddu[a] = cam->defocus_disk_u[a];
         P.ddv[a] = cam->defocus_disk_v[a];
     }
+}
+
+void fill_params(const rt_ctx* c, const rt_camera* cam, int spp, int max_depth, int mesh_stack, RenderParams& P) {
+    std::memset(&P, 0, sizeof(P));
+    fill_camera(c, cam, P);
+    P.spp = spp;
+    P.max_depth = max_depth;
+    P.tiles_x = (P.W + 7) / 8;
+    P.tiles_x_inv = 1.0 / P.tiles_x;
+    P.tiles_x_inv_half = 0.5 * P.tiles_x_inv;
+    P.n_nodes = c->n_nodes;
+    P.n_spheres = c->n_sph;
+    P.n_mats = c->n_mat;
+    P.n_big = c->n_big;
+    P.n_front = c->n_front;
+    P.stack_size = stack_entries(c);
     P.nodes = c->d_nodes;
     P.spheres = c->d_sph;
     P.mats = c->d_mat;
@@ -249,6 +255,13 @@ void rt_destroy(rt_ctx* c) {
     (void)hipFree(c->d_samples);
     (void)hipFree(c->d_queue64);
     (void)hipFree(c->d_queue_rad);
+    (void)hipFree(c->d_px_offsets);
+    (void)hipFree(c->d_px_scan);
+    (void)hipFree(c->d_queue_px);
+    (void)hipFree(c->d_px_acc);
+    (void)hipFree(c->d_px_flags);
+    (void)hipFree(c->d_px_samples);
+    (void)hipFree(c->d_px_sseg);
     (void)hipFree(c->d_gather);
     for (auto& a : c->accum) {
         (void)hipFree(a.acc);
@@ -997,12 +1010,13 @@ int rt_render_frame_multi(rt_ctx** cs, int n, const rt_camera* cam, int spp, int
 }
 
 // The per-ray query launches (rt_trace_rays*, rt_occluded): the scene's tree in LDS at
-// TRACE_BLOCK threads, and its size there with the mesh stack's LDS columns.
-static int query_setup(rt_ctx* c, const char* what, RenderParams& P, size_t& lds) {
+// TRACE_BLOCK threads, and its size there with the mesh stack's LDS columns.  view: the camera
+// of a query that makes its own rays (rt_render_pixels), else none.
+static int query_setup(rt_ctx* c, const char* what, RenderParams& P, size_t& lds, const rt_camera* view = nullptr) {
     HIPCHK(c, hipSetDevice(c->device));
     rt_camera cam{};
     cam.image_width = cam.image_height = 1;
-    fill_params(c, &cam, 1, 1, plan_launch(c, true).mesh_stack, P);
+    fill_params(c, view ? view : &cam, 1, 1, plan_launch(c, true).mesh_stack, P);
     P.nodes = c->d_nodes;   // (the time-binned copies are a render-kernel option)
     lds = lds_scene_bytes_at(c, TRACE_BLOCK) + (size_t)TRACE_BLOCK * (size_t)P.mstack * 4;
     if (lds > 160 * 1024) return fail(c, RT_ERR_LIMIT, "%s needs %zu B of LDS per workgroup", what, lds);
@@ -1085,6 +1099,129 @@ int rt_radiance_rays(rt_ctx* c, const void* rays, int n, const rt_path_key* keys
                     : launch_radiance_f32(P, lds, st, rays, n, keys, radiance, segments, c->n_cu);
     }
     if (e != hipSuccess) return fail(c, RT_ERR_HIP, "radiance launch: %s", hipGetErrorString(e));
+    HIPCHK(c, hipEventRecord(c->ev1, st));
+    c->timed = true;
+    return RT_OK;
+}
+
+// rt_render_pixels / rt_camera_rays: offsets = the exclusive scan of the valid jobs' counts on
+// `st` (c->d_px_offsets), and T = offsets[num_jobs] read back -- the calls' one synchronisation.
+static int pixel_scan(rt_ctx* c, const rt_camera* cam, const rt_pixel_job* jobs, int num_jobs, hipStream_t st,
+                      unsigned long long& total) {
+    int rc;
+    if ((rc = grow(c, (void**)&c->d_px_offsets, &c->px_offsets_cap, ((size_t)num_jobs + 1) * sizeof(unsigned long long))))
+        return rc;
+    const uint32_t npix = (uint32_t)((long long)cam->image_width * cam->image_height);   // (check_camera: < 2^29)
+    size_t tmp = 0;
+    HIPCHK(c, launch_pixel_scan(jobs, num_jobs, npix, c->d_px_offsets, nullptr, &tmp, st));
+    if ((rc = grow(c, &c->d_px_scan, &c->px_scan_cap, tmp))) return rc;
+    HIPCHK(c, launch_pixel_scan(jobs, num_jobs, npix, c->d_px_offsets, c->d_px_scan, &tmp, st));
+    HIPCHK(c, hipMemcpyAsync(&total, c->d_px_offsets + num_jobs, sizeof(total), hipMemcpyDeviceToHost, st));
+    HIPCHK(c, hipStreamSynchronize(st));
+    return RT_OK;
+}
+
+int rt_camera_rays(rt_ctx* c, const rt_camera* cam, const rt_pixel_job* jobs, int num_jobs, void* rays,
+                   rt_path_key* keys, int32_t* ray_job, int64_t max_rays, int64_t* num_rays, void* stream) {
+    if (!c) return RT_ERR_INVALID;
+    int rc = check_camera(c, cam);
+    if (rc) return rc;
+    if (num_jobs < 0 || (num_jobs > 0 && (!jobs || !rays || !keys)))
+        return fail(c, RT_ERR_INVALID, "rt_camera_rays: %d jobs, jobs %p, rays %p, keys %p", num_jobs, (const void*)jobs,
+                    rays, (void*)keys);
+    if (num_jobs == 0) {
+        if (num_rays) *num_rays = 0;
+        return RT_OK;
+    }
+    HIPCHK(c, hipSetDevice(c->device));
+    hipStream_t st = stream ? (hipStream_t)stream : c->stream;
+    HIPCHK(c, hipEventRecord(c->ev0, st));
+    unsigned long long total = 0;
+    if ((rc = pixel_scan(c, cam, jobs, num_jobs, st, total))) return rc;
+    if (num_rays) *num_rays = (int64_t)total;
+    if (total > 0x7fffffffull) return fail(c, RT_ERR_LIMIT, "rt_camera_rays: %llu samples (> 2^31 - 1)", total);
+    if ((int64_t)total > max_rays)
+        return fail(c, RT_ERR_INVALID, "rt_camera_rays: %llu rays for buffers of %lld", total, (long long)max_rays);
+    RenderParams P;
+    std::memset(&P, 0, sizeof(P));
+    fill_camera(c, cam, P);
+    const hipError_t e =
+        c->precision == RT_PREC_F64
+            ? launch_camera_rays_f64(P, st, jobs, c->d_px_offsets, num_jobs, (long long)total, rays, keys, ray_job)
+            : launch_camera_rays_f32(P, st, jobs, c->d_px_offsets, num_jobs, (long long)total, rays, keys, ray_job);
+    if (e != hipSuccess) return fail(c, RT_ERR_HIP, "camera-ray launch: %s", hipGetErrorString(e));
+    HIPCHK(c, hipEventRecord(c->ev1, st));
+    c->timed = true;
+    return RT_OK;
+}
+
+int rt_render_pixels(rt_ctx* c, const rt_camera* cam, const rt_pixel_job* jobs, int num_jobs, int max_depth,
+                     int accumulate, void* out_sums, uint32_t* out_segments, void* stream) {
+    if (!c) return RT_ERR_INVALID;
+    if (!c->has_scene) return fail(c, RT_ERR_NO_SCENE, "rt_render_pixels before rt_upload_scene");
+    int rc = check_camera(c, cam);
+    if (rc) return rc;
+    if (num_jobs < 0 || (num_jobs > 0 && (!jobs || !out_sums)))
+        return fail(c, RT_ERR_INVALID, "rt_render_pixels: %d jobs, jobs %p, out_sums %p", num_jobs, (const void*)jobs,
+                    out_sums);
+    const bool f64 = c->precision == RT_PREC_F64;
+    if (f64 && max_depth > 64)
+        return fail(c, RT_ERR_LIMIT, "fp64 path keeps at most 64 bounces (max_depth %d)", max_depth);
+    RenderParams P;
+    size_t lds;
+    if ((rc = query_setup(c, "rt_render_pixels", P, lds, cam))) return rc;
+    if (num_jobs == 0) return RT_OK;
+    P.max_depth = max_depth;
+    const size_t nj = (size_t)num_jobs;
+    if (!c->d_queue_px) HIPCHK(c, hipMalloc((void**)&c->d_queue_px, QUEUE_CTRL_BYTES));
+    P.queue = c->d_queue_px;
+    hipStream_t st = stream ? (hipStream_t)stream : c->stream;
+    HIPCHK(c, hipEventRecord(c->ev0, st));
+    hipError_t e = hipSuccess;
+    if (max_depth <= 0) {   // camera_cpu.h:9-10: no path, no light; accumulate: nothing to add
+        if (!accumulate) {
+            e = hipMemsetAsync(out_sums, 0, nj * 3 * elem_bytes(c), st);
+            if (e == hipSuccess && out_segments) e = hipMemsetAsync(out_segments, 0, nj * sizeof(uint32_t), st);
+        }
+    } else {
+        unsigned long long total = 0;
+        if ((rc = pixel_scan(c, cam, jobs, num_jobs, st, total))) return rc;
+        if (total > 0x7fffffffull) return fail(c, RT_ERR_LIMIT, "rt_render_pixels: %llu samples (> 2^31 - 1)", total);
+        const unsigned long long* off = c->d_px_offsets;
+        if (!f64) {
+            if ((rc = grow(c, (void**)&c->d_px_acc, &c->px_acc_cap, nj * 3 * sizeof(long long)))) return rc;
+            if ((rc = grow(c, (void**)&c->d_px_flags, &c->px_flags_cap, nj * sizeof(uint32_t)))) return rc;
+            e = launch_pixels_seed(off, num_jobs, accumulate ? 1 : 0, (const float*)out_sums, c->d_px_acc, c->d_px_flags,
+                                   out_segments, st);
+            if (e == hipSuccess) e = hipMemsetAsync(c->d_queue_px, 0, QUEUE_CTRL_BYTES, st);
+            if (e == hipSuccess)
+                e = launch_pixels_f32(P, lds, st, jobs, off, num_jobs, total, 0, (int)total, (unsigned long long*)c->d_px_acc,
+                                      c->d_px_flags, out_segments, c->n_cu);
+            if (e == hipSuccess)
+                e = launch_pixels_finalize(off, num_jobs, accumulate ? 1 : 0, c->d_px_acc, c->d_px_flags,
+                                           (float*)out_sums, st);
+        } else {
+            // passes of at most floor(sample_buffer_mb 2^20 / 28) samples, reduced in order; the
+            // first one also zeroes the jobs without samples, so it runs even when T = 0
+            const unsigned long long fit = ((unsigned long long)c->tuning.sample_buffer_mb << 20) / PX_SAMPLE_BYTES;
+            const unsigned long long pass = std::max(1ull, std::min(fit, total));
+            if ((rc = grow(c, (void**)&c->d_px_samples, &c->px_samples_cap, (size_t)pass * 3 * sizeof(double)))) return rc;
+            if ((rc = grow(c, (void**)&c->d_px_sseg, &c->px_sseg_cap, (size_t)pass * sizeof(uint32_t)))) return rc;
+            unsigned long long q0 = 0;
+            do {
+                const unsigned long long q1 = std::min(total, q0 + pass);
+                e = hipMemsetAsync(c->d_queue_px, 0, QUEUE_CTRL_BYTES, st);
+                if (e == hipSuccess)
+                    e = launch_pixels_f64(P, lds, st, jobs, off, num_jobs, total, q0, (int)(q1 - q0), c->d_px_samples,
+                                          c->d_px_sseg, c->n_cu);
+                if (e == hipSuccess)
+                    e = launch_pixels_reduce(off, num_jobs, q0, q1, c->d_px_samples, c->d_px_sseg, accumulate ? 1 : 0,
+                                             (double*)out_sums, out_segments, st);
+                q0 = q1;
+            } while (q0 < total && e == hipSuccess);
+        }
+    }
+    if (e != hipSuccess) return fail(c, RT_ERR_HIP, "pixel render launch: %s", hipGetErrorString(e));
     HIPCHK(c, hipEventRecord(c->ev1, st));
     c->timed = true;
     return RT_OK;

@@ -84,7 +84,24 @@ struct rt_ctx {
     uint32_t* d_queue64 = nullptr;   // fp64 persistent lanes (f64_kernel 3): work-queue control block
     uint32_t* d_queue_rad = nullptr;   // rt_radiance_rays: the launch's per-XCD heads (a control block of its own)
     size_t samples_cap = 0;
-    void* d_gather = nullptr;   // rt_render_frame_multi: all contexts' shards
+    // rt_render_pixels / rt_camera_rays (grown on demand): the scan's offsets (num_jobs + 1 x 8 B)
+    // and work space, a control block of per-XCD heads of their own, fp32: the per-job
+    // fixed-point sums (num_jobs x 3) and flags, fp64: one pass's samples (x 3 doubles) and
+    // segment counts
+    unsigned long long* d_px_offsets = nullptr;
+    size_t px_offsets_cap = 0;
+    void* d_px_scan = nullptr;
+    size_t px_scan_cap = 0;
+    uint32_t* d_queue_px = nullptr;
+    long long* d_px_acc = nullptr;
+    size_t px_acc_cap = 0;
+    uint32_t* d_px_flags = nullptr;
+    size_t px_flags_cap = 0;
+    double* d_px_samples = nullptr;
+    size_t px_samples_cap = 0;
+    uint32_t* d_px_sseg = nullptr;
+    size_t px_sseg_cap = 0;
+    void* d_gather = nullptr;  // rt_render_frame_multi: all contexts' shards
     size_t gather_cap = 0;
 
     // fp32 fixed-point pixel sums (RenderParams::accum), one slot per output buffer the

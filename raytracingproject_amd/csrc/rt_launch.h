@@ -56,6 +56,50 @@ hipError_t launch_radiance_f32(const RenderParams& P, size_t lds_bytes, hipStrea
                                const void* keys, void* radiance, uint32_t* segments, int n_cu);
 hipError_t launch_radiance_f64(const RenderParams& P, size_t lds_bytes, hipStream_t stream, const void* rays, int n,
                                const void* keys, void* radiance, uint32_t* segments, int n_cu);
+// bytes of one fp64 sample record (3 doubles + one uint32, kept in two arrays): a pass of
+// rt_render_pixels holds floor(sample_buffer_mb 2^20 / PX_SAMPLE_BYTES) samples
+constexpr size_t PX_SAMPLE_BYTES = 28;
+// sparse rendering (rt_render_pixels, rt_camera_rays; csrc/rt_pixels.h).  jobs: num_jobs
+// rt_pixel_job (device); offsets: num_jobs + 1 64-bit values (device).
+// launch_pixel_scan: offsets = the exclusive scan of the valid jobs' sample counts (pixel <
+// npix, else 0), offsets[num_jobs] = T.  temp == null: only *temp_bytes is set, to what the
+// scan needs; nothing is launched.
+hipError_t launch_pixel_scan(const void* jobs, int num_jobs, uint32_t npix, unsigned long long* offsets, void* temp,
+                             size_t* temp_bytes, hipStream_t stream);
+// rt_camera_rays: flat samples [0, total) -> rays (7 values each), keys (rt_path_key), ray_job
+// (may be null); P carries the camera and the seed only
+hipError_t launch_camera_rays_f32(const RenderParams& P, hipStream_t stream, const void* jobs,
+                                  const unsigned long long* offsets, int num_jobs, long long total, void* rays,
+                                  void* keys, int32_t* ray_job);
+hipError_t launch_camera_rays_f64(const RenderParams& P, hipStream_t stream, const void* jobs,
+                                  const unsigned long long* offsets, int num_jobs, long long total, void* rays,
+                                  void* keys, int32_t* ray_job);
+// the fused path kernel over flat samples [q_begin, q_begin + n) of the list's `total`
+// (= offsets[num_jobs]): persistent lanes as
+// launch_radiance_* (P.queue zeroed by the caller, P.max_depth >= 1, the camera in P).
+// fp32 adds into acc (num_jobs x 3 sums in units of 2^-28), flags (num_jobs) and segments
+// (num_jobs, may be null); fp64 stores sample q at q - q_begin of samples (n x 3 doubles) and
+// sample_segs (n).
+hipError_t launch_pixels_f32(const RenderParams& P, size_t lds_bytes, hipStream_t stream, const void* jobs,
+                             const unsigned long long* offsets, int num_jobs, unsigned long long total,
+                             unsigned long long q_begin, int n,
+                             unsigned long long* acc, uint32_t* flags, uint32_t* segments, int n_cu);
+hipError_t launch_pixels_f64(const RenderParams& P, size_t lds_bytes, hipStream_t stream, const void* jobs,
+                             const unsigned long long* offsets, int num_jobs, unsigned long long total,
+                             unsigned long long q_begin, int n,
+                             double* samples, uint32_t* sample_segs, int n_cu);
+// fp64: one pass's samples [q_begin, q_end) into out_sums / out_segments (may be null), per job
+// in sample order (pixels_reduce_kernel)
+hipError_t launch_pixels_reduce(const unsigned long long* offsets, int num_jobs, unsigned long long q_begin,
+                                unsigned long long q_end, const double* samples, const uint32_t* sample_segs,
+                                int accumulate, double* out_sums, uint32_t* out_segments, hipStream_t stream);
+// fp32: the per-job fixed-point sums before the path kernel -- 0, or (accumulate, valid jobs)
+// seeded from out_sums as seed_accum_kernel does; out_segments (may be null) zeroed unless
+// accumulate -- and after it: acc, flags -> out_sums (accumulate: valid jobs only)
+hipError_t launch_pixels_seed(const unsigned long long* offsets, int num_jobs, int accumulate, const float* out_sums,
+                              long long* acc, uint32_t* flags, uint32_t* out_segments, hipStream_t stream);
+hipError_t launch_pixels_finalize(const unsigned long long* offsets, int num_jobs, int accumulate,
+                                  const long long* acc, const uint32_t* flags, float* out_sums, hipStream_t stream);
 hipError_t launch_tape_f64(const RenderParams& P, int max_depth, const double* ray7, const double* tape, int tape_len,
                            double* out, int* used, hipStream_t stream);
 // element: 4 (float/uint32) or 8 (double); channels: 1 or 3

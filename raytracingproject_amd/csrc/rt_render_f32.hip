@@ -6,6 +6,7 @@
 
 #include "rt_occluded.h"   // (includes rt_render_impl.h)
 #include "rt_radiance.h"
+#include "rt_pixels.h"
 
 namespace rtx {
 
@@ -161,6 +162,40 @@ hipError_t launch_radiance_f32(const RenderParams& P, size_t lds_bytes, hipStrea
         hipLaunchKernelGGL(kern, dim3(radiance_grid<B>(v, lds_bytes, n, n_cu)), dim3(B), lds_bytes, stream, P, r, n,
                            k, o, segments);
     }
+    return hipGetLastError();
+}
+
+// Sparse rendering (rt_render_pixels), fp32: launch_radiance_f32's flags, register budgets and
+// grid; the camera and the job search are live only while a lane takes a sample.
+hipError_t launch_pixels_f32(const RenderParams& P, size_t lds_bytes, hipStream_t stream, const void* jobs,
+                             const unsigned long long* offsets, int num_jobs, unsigned long long total,
+                             unsigned long long q_begin, int n,
+                             unsigned long long* acc, uint32_t* flags, uint32_t* segments, int n_cu) {
+    if (n <= 0) return hipSuccess;
+    constexpr int B = TRACE_BLOCK;
+    constexpr int TS = TRAV_SELROOT | TRAV_B128 | TRAV_CULL, TM = TRAV_SELROOT | TRAV_CULL | TRAV_MIFIF;
+    const PixelJob* j = (const PixelJob*)jobs;
+    if (P.n_mnodes > 0) {
+        auto* kern = pixels_kernel<float, false, B, RADIANCE_MESH_WPE, TM, true>;
+        static const int v = radiance_vgprs((const void*)kern);
+        hipLaunchKernelGGL(kern, dim3(radiance_grid<B>(v, lds_bytes, n, n_cu)), dim3(B), lds_bytes, stream, P, j,
+                           offsets, num_jobs, total, q_begin, n, acc, flags, segments, (float*)nullptr, (uint32_t*)nullptr);
+    } else {
+        auto* kern = pixels_kernel<float, false, B, RADIANCE_WPE, TS, false>;
+        static const int v = radiance_vgprs((const void*)kern);
+        hipLaunchKernelGGL(kern, dim3(radiance_grid<B>(v, lds_bytes, n, n_cu)), dim3(B), lds_bytes, stream, P, j,
+                           offsets, num_jobs, total, q_begin, n, acc, flags, segments, (float*)nullptr, (uint32_t*)nullptr);
+    }
+    return hipGetLastError();
+}
+
+hipError_t launch_camera_rays_f32(const RenderParams& P, hipStream_t stream, const void* jobs,
+                                  const unsigned long long* offsets, int num_jobs, long long total, void* rays,
+                                  void* keys, int32_t* ray_job) {
+    if (total <= 0) return hipSuccess;
+    const int grid = (int)std::min<long long>((total + 255) / 256, 65536);
+    hipLaunchKernelGGL(camera_rays_kernel<float>, dim3(grid), dim3(256), 0, stream, P, (const PixelJob*)jobs, offsets,
+                       num_jobs, total, (float*)rays, (PathKey*)keys, ray_job);
     return hipGetLastError();
 }
 

@@ -3,6 +3,9 @@
 // precision-agnostic kernels (unshard, quantize).
 #include "rt_occluded.h"   // (includes rt_render_impl.h)
 #include "rt_radiance.h"
+#include "rt_pixels.h"
+
+#include <hipcub/hipcub.hpp>
 
 namespace rtx {
 
@@ -301,6 +304,110 @@ hipError_t launch_finalize(long long* accum, const unsigned long long* packed, c
     if (n == 0) return hipSuccess;
     hipLaunchKernelGGL(finalize_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, accum, packed, flags,
                        out, n);
+    return hipGetLastError();
+}
+
+// ---- sparse rendering (rt_render_pixels, rt_camera_rays; rt_pixels.h) -----------------------
+hipError_t launch_pixel_scan(const void* jobs, int num_jobs, uint32_t npix, unsigned long long* offsets, void* temp,
+                             size_t* temp_bytes, hipStream_t stream) {
+    const PixelJobCount count{(const PixelJob*)jobs, num_jobs, npix};
+    hipcub::CountingInputIterator<int> idx(0);
+    hipcub::TransformInputIterator<unsigned long long, PixelJobCount, hipcub::CountingInputIterator<int>> in(idx, count);
+    return hipcub::DeviceScan::ExclusiveSum(temp, *temp_bytes, in, offsets, num_jobs + 1, stream);
+}
+
+hipError_t launch_camera_rays_f64(const RenderParams& P, hipStream_t stream, const void* jobs,
+                                  const unsigned long long* offsets, int num_jobs, long long total, void* rays,
+                                  void* keys, int32_t* ray_job) {
+    if (total <= 0) return hipSuccess;
+    const int grid = (int)((total + 255) / 256 < 65536 ? (total + 255) / 256 : 65536);
+    hipLaunchKernelGGL(camera_rays_kernel<double>, dim3(grid), dim3(256), 0, stream, P, (const PixelJob*)jobs, offsets,
+                       num_jobs, total, (double*)rays, (PathKey*)keys, ray_job);
+    return hipGetLastError();
+}
+
+// Sparse rendering (rt_render_pixels), fp64: launch_radiance_f64's box tests, register budget
+// and grid.
+hipError_t launch_pixels_f64(const RenderParams& P, size_t lds_bytes, hipStream_t stream, const void* jobs,
+                             const unsigned long long* offsets, int num_jobs, unsigned long long total,
+                             unsigned long long q_begin, int n,
+                             double* samples, uint32_t* sample_segs, int n_cu) {
+    if (n <= 0) return hipSuccess;
+    constexpr int B = TRACE_BLOCK;
+    const PixelJob* j = (const PixelJob*)jobs;
+    if (P.n_mnodes > 0) {
+        auto* kern = pixels_kernel<double, true, B, 4, TRAV_F32BOX, true>;
+        static const int v = radiance_vgprs((const void*)kern);
+        hipLaunchKernelGGL(kern, dim3(radiance_grid<B>(v, lds_bytes, n, n_cu)), dim3(B), lds_bytes, stream, P, j,
+                           offsets, num_jobs, total, q_begin, n, (unsigned long long*)nullptr, (uint32_t*)nullptr,
+                           (uint32_t*)nullptr, samples, sample_segs);
+    } else {
+        auto* kern = pixels_kernel<double, true, B, 4, TRAV_F32BOX, false>;
+        static const int v = radiance_vgprs((const void*)kern);
+        hipLaunchKernelGGL(kern, dim3(radiance_grid<B>(v, lds_bytes, n, n_cu)), dim3(B), lds_bytes, stream, P, j,
+                           offsets, num_jobs, total, q_begin, n, (unsigned long long*)nullptr, (uint32_t*)nullptr,
+                           (uint32_t*)nullptr, samples, sample_segs);
+    }
+    return hipGetLastError();
+}
+
+hipError_t launch_pixels_reduce(const unsigned long long* offsets, int num_jobs, unsigned long long q_begin,
+                                unsigned long long q_end, const double* samples, const uint32_t* sample_segs,
+                                int accumulate, double* out_sums, uint32_t* out_segments, hipStream_t stream) {
+    if (num_jobs <= 0) return hipSuccess;
+    hipLaunchKernelGGL(pixels_reduce_kernel<double>, dim3((unsigned)((num_jobs + 255) / 256)), dim3(256), 0, stream,
+                       offsets, num_jobs, q_begin, q_end, samples, sample_segs, accumulate, out_sums, out_segments);
+    return hipGetLastError();
+}
+
+// fp32, one thread per job, before the path kernel: the job's fixed-point sums start at 0, or
+// (accumulate, a job that has samples) where out_sums stands, as seed_accum_kernel rounds it.
+__global__ void px_seed_kernel(const unsigned long long* __restrict__ offsets, int num_jobs, int accumulate,
+                               const float* __restrict__ out, long long* __restrict__ acc,
+                               uint32_t* __restrict__ flags, uint32_t* __restrict__ out_segs) {
+    const int k = blockIdx.x * blockDim.x + threadIdx.x;
+    if (k >= num_jobs) return;
+    uint32_t fl = 0;
+    const bool cont = accumulate && offsets[k] != offsets[k + 1];
+    for (int c = 0; c < 3; ++c) {
+        long long a = 0;
+        if (cont) {
+            const double v = rint((double)out[(size_t)k * 3 + c] * (double)(1ll << FIX_SHIFT));
+            if (fabs(v) < 0x1p62)
+                a = (long long)v;
+            else
+                fl |= (v != v ? FIX_NAN : v > 0 ? FIX_POS : FIX_NEG) << (3 * c);
+        }
+        acc[(size_t)k * 3 + c] = a;
+    }
+    flags[k] = fl;
+    if (out_segs && !accumulate) out_segs[k] = 0;
+}
+
+// ... and after it: the sums as floats (finalize_kernel's value); with accumulate a job
+// without samples keeps what out_sums holds.
+__global__ void px_finalize_kernel(const unsigned long long* __restrict__ offsets, int num_jobs, int accumulate,
+                                   const long long* __restrict__ acc, const uint32_t* __restrict__ flags,
+                                   float* __restrict__ out) {
+    const int k = blockIdx.x * blockDim.x + threadIdx.x;
+    if (k >= num_jobs) return;
+    if (accumulate && offsets[k] == offsets[k + 1]) return;
+    for (int c = 0; c < 3; ++c) out[(size_t)k * 3 + c] = finalized(acc[(size_t)k * 3 + c], (flags[k] >> (3 * c)) & 7u);
+}
+
+hipError_t launch_pixels_seed(const unsigned long long* offsets, int num_jobs, int accumulate, const float* out_sums,
+                              long long* acc, uint32_t* flags, uint32_t* out_segments, hipStream_t stream) {
+    if (num_jobs <= 0) return hipSuccess;
+    hipLaunchKernelGGL(px_seed_kernel, dim3((unsigned)((num_jobs + 255) / 256)), dim3(256), 0, stream, offsets,
+                       num_jobs, accumulate, out_sums, acc, flags, out_segments);
+    return hipGetLastError();
+}
+
+hipError_t launch_pixels_finalize(const unsigned long long* offsets, int num_jobs, int accumulate,
+                                  const long long* acc, const uint32_t* flags, float* out_sums, hipStream_t stream) {
+    if (num_jobs <= 0) return hipSuccess;
+    hipLaunchKernelGGL(px_finalize_kernel, dim3((unsigned)((num_jobs + 255) / 256)), dim3(256), 0, stream, offsets,
+                       num_jobs, accumulate, acc, flags, out_sums);
     return hipGetLastError();
 }
 
