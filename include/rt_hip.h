@@ -178,7 +178,8 @@ typedef struct {
                                persistent lanes over the work queue (item_* below) */
     int32_t sample_buffer_mb;  /* F64: cap of the per-sample radiance buffer (MiB) of kernels 3 / 4; longer
                                sample ranges run in passes, each of at most 65535 samples (the coherent
-                               kernel's FIFO keeps a sample's index within its pass in 16 bits) */
+                               kernel's FIFO keeps a sample's index within its pass in 16 bits) and at
+                               least one; >= 1 (>= 16 before rt_render_pixels_moments) */
     int32_t mesh_builder;   /* RT_MESH_BUILD_HOST: binned SAH on the host (best trees); RT_MESH_BUILD_GPU:
                                built on the device -- Morton-code LBVH, then two rounds of treelet
                                restructuring by SAH (r06, ABI 10; fast builds for large or changing
@@ -532,6 +533,65 @@ typedef struct {
 } rt_pixel_job;
 int rt_render_pixels(rt_ctx* ctx, const rt_camera* cam, const rt_pixel_job* jobs, int num_jobs, int max_depth,
                      int accumulate, void* out_sums, uint32_t* out_segments, void* stream);
+/* rt_render_pixels with a second output, the per-job second moment -- what an adaptive sampler
+ * needs to estimate a pixel's variance on the device.  The contract is rt_render_pixels': jobs,
+ * flat sample list, T, the fp64 passes, the single synchronisation, the errors, max_depth <= 0,
+ * invalid and empty jobs; out_sums and out_segments are bit for bit what rt_render_pixels writes
+ * for the same arguments.
+ * out_sumsq: device memory, num_jobs x 3 values of the context precision: per channel the sum of
+ * squares of the job's per-sample radiance.  Required: NULL with num_jobs > 0 is RT_ERR_INVALID.
+ * A job without samples gets 0, or is left untouched with accumulate = 1.
+ * fp64 contexts: sumsq = start + L0 L0 + L1 L1 + ..., in sample order; each product is rounded to
+ * double on its own (never fused into the addition), the additions are sequential; start = 0.0,
+ * or (accumulate = 1) the value already in out_sumsq.  A job that straddles a pass continues
+ * out_sumsq as it continues out_sums, so {p, 0, a} then {p, a, b} with accumulate equals
+ * {p, 0, a + b} in both outputs.
+ * fp32 contexts: per sample channel r = rintf(L 2^19), the integer-valued float the sum rule
+ * rounds to.  r == 0 adds nothing; a NaN r makes the channel's sumsq NaN; |r| >= 2^32 (a sample
+ * at or beyond the documented exact range 2^13, or an infinity) makes it +inf (NaN wins over
+ * +inf); otherwise r r is an exact integer below 2^64 and is added exactly, in any order: two
+ * 64-bit words per channel, S_lo += r r & 0xffffffff and S_hi += r r >> 32, neither of which can
+ * overflow within 2^31 samples, and out_sumsq = (float)(((double)S_hi 2^32 + (double)S_lo) 2^-38),
+ * IEEE operations in that order.  accumulate = 1 starts from X = rint((double)out_sumsq 2^38)
+ * for 0 <= out_sumsq < 2^57 (S_hi = X >> 32, S_lo = X & 0xffffffff); a negative or NaN start gives
+ * NaN, one >= 2^57 or +inf gives +inf.  The sums' own rule and flags are untouched.
+ * Cost: fp32 adds up to six atomics per sample to rt_render_pixels' three; fp64 adds three
+ * multiplications per sample to the ordered reduction.  rt_tuning.grid_workgroups > 0 caps the
+ * path kernel's grid here (rt_render_pixels ignores it); the outputs do not depend on it.
+ * Added to ABI 12 without a version bump. */
+int rt_render_pixels_moments(rt_ctx* ctx, const rt_camera* cam, const rt_pixel_job* jobs, int num_jobs, int max_depth,
+                             int accumulate, void* out_sums, void* out_sumsq, uint32_t* out_segments, void* stream);
+/* One round of an adaptive sampler, on the device: rewrites jobs[k] in place for the next
+ * rt_render_pixels_moments call from the sums and second moments the list has accumulated.  The
+ * list keeps its length and slot order, so out_sums, out_sumsq and out_segments stay valid as
+ * accumulators (accumulate = 1); a converged slot gets sample_count = 0, which rt_render_pixels*
+ * leaves alone.  sums, sumsq: num_jobs x 3 values of the context precision (device).
+ * All arithmetic is fp64 whatever the context precision (floats convert exactly); every
+ * operation is rounded once, in the written order, nothing is fused.  With n = sample_begin +
+ * sample_count (64-bit), s_c = sums[k][c], q_c = sumsq[k][c]:
+ *   n >= max_samples: next = 0;  else n < min_samples: next = min_samples - n;
+ *   else any s_c or q_c non-finite: not converged;
+ *   else m_c = s_c / n, d_c = q_c - s_c m_c, v_c = d_c > 0 ? d_c / (n - 1) : 0,
+ *        e2 = ((v_0 + v_1) + v_2) / (3 n), m = ((m_0 + m_1) + m_2) / 3, a = max(|m|, abs_floor),
+ *        t = rel_error a; converged iff e2 <= t t  (the squared standard error of the mean of the
+ *        channel average against a relative tolerance);
+ *   not converged: next = min(n, max_step, max_samples - n) (doubling, capped); converged: 0.
+ *   jobs[k] = {pixel, (uint32)n, next, 0}.
+ * stats: two device uint64, overwritten: {jobs with next > 0, the sum of next}.
+ * Errors: RT_ERR_INVALID for a NULL pointer with num_jobs > 0, num_jobs < 0, min_samples < 2,
+ * min_samples > max_samples, max_samples > 2^31 - 1, max_step == 0, a negative or non-finite
+ * rel_error or abs_floor.  num_jobs == 0 is a no-op that zeroes stats.  Needs no scene;
+ * asynchronous on `stream` (NULL: the context's); rt_last_kernel_ms times it.
+ * Not done here: compacting the job list (converged slots stay, at 16 bytes and one scan element
+ * each), a fused finish kernel for a non-uniform n (divide sums by n yourself; rt_quantize(mean,
+ * spp = 1) quantises), walking the sphere grid from queries, any use from rt_render.
+ * Added to ABI 12 without a version bump. */
+typedef struct {
+    double rel_error, abs_floor;
+    uint32_t min_samples, max_samples, max_step, pad;
+} rt_adaptive_params;
+int rt_refine_jobs(rt_ctx* ctx, rt_pixel_job* jobs, int num_jobs, const void* sums, const void* sumsq,
+                   const rt_adaptive_params* params, uint64_t* stats, void* stream);
 /* The camera's rays on the device: camera::get_ray (camera.h:87-113) for every sample of a job
  * list (jobs, flat sample list and T as for rt_render_pixels).  For flat sample q: rays[q] = the
  * ray, 7 values of the context precision {origin xyz, direction xyz, time}, in the render

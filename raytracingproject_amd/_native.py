@@ -87,6 +87,12 @@ class RtTuning(C.Structure):
 
 
 # name -> (restype, argtypes); the full exported surface of include/rt_hip.h
+class RtAdaptiveParams(C.Structure):
+    """rt_adaptive_params (32 B): rt_refine_jobs' stopping rule and step caps."""
+    _fields_ = [("rel_error", C.c_double), ("abs_floor", C.c_double), ("min_samples", C.c_uint32),
+                ("max_samples", C.c_uint32), ("max_step", C.c_uint32), ("pad", C.c_uint32)]
+
+
 SIGNATURES = {
     "rt_abi_version": (C.c_int, []),
     "rt_device_count": (C.c_int, []),
@@ -144,6 +150,10 @@ SIGNATURES = {
                                    C.c_void_p, C.c_void_p]),   # ABI 12
     "rt_camera_rays": (C.c_int, [C.c_void_p, C.POINTER(RtCamera), C.c_void_p, C.c_int, C.c_void_p, C.c_void_p,
                                  C.c_void_p, C.c_int64, C.POINTER(C.c_int64), C.c_void_p]),   # ABI 12
+    "rt_render_pixels_moments": (C.c_int, [C.c_void_p, C.POINTER(RtCamera), C.c_void_p, C.c_int, C.c_int, C.c_int,
+                                           C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),   # ABI 12
+    "rt_refine_jobs": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.POINTER(RtAdaptiveParams),
+                                 C.c_void_p, C.c_void_p]),   # ABI 12
 }
 
 # rt_pixel_job (16 B): rt_render_pixels' / rt_camera_rays' job -- samples [sample_begin, +sample_count) of a pixel
@@ -578,6 +588,59 @@ class Renderer:
         self._check(self._L.rt_render_pixels(self.ctx, C.byref(cam), C.c_void_p(jobs_dev or 0), n, max_depth,
                                              1 if accumulate else 0, C.c_void_p(out_dev or 0),
                                              C.c_void_p(seg_dev or 0), C.c_void_p(stream or 0)), "rt_render_pixels")
+
+    def render_pixels_moments(self, cam: RtCamera, jobs_dev: int, n: int, max_depth: int, out_dev: int, sumsq_dev: int,
+                              seg_dev: int | None = None, accumulate: bool = False, stream: int | None = None) -> None:
+        """rt_render_pixels_moments: render_pixels with the per-job second moment, n x 3 sums of
+        squares of the context precision (device), beside the sums."""
+        self._check(self._L.rt_render_pixels_moments(self.ctx, C.byref(cam), C.c_void_p(jobs_dev or 0), n, max_depth,
+                                                     1 if accumulate else 0, C.c_void_p(out_dev or 0),
+                                                     C.c_void_p(sumsq_dev or 0), C.c_void_p(seg_dev or 0),
+                                                     C.c_void_p(stream or 0)), "rt_render_pixels_moments")
+
+    def refine_jobs(self, jobs_dev: int, n: int, sums_dev: int, sumsq_dev: int, params: RtAdaptiveParams,
+                    stats_dev: int, stream: int | None = None) -> None:
+        """rt_refine_jobs: rewrites n jobs (device) in place for the next round from their sums and
+        second moments (n x 3 of the context precision, device); stats_dev: two uint64 (device) ->
+        {jobs that go on, samples they ask for}.  Asynchronous."""
+        self._check(self._L.rt_refine_jobs(self.ctx, C.c_void_p(jobs_dev or 0), n, C.c_void_p(sums_dev or 0),
+                                           C.c_void_p(sumsq_dev or 0), C.byref(params), C.c_void_p(stats_dev or 0),
+                                           C.c_void_p(stream or 0)), "rt_refine_jobs")
+
+    def render_adaptive(self, cam: RtCamera, max_depth: int, rel_error: float, abs_floor: float = 0.0,
+                        min_samples: int = 16, max_samples: int = 256, max_step: int | None = None):
+        """Adaptive sampling of a whole frame: one job per pixel in row-major order (slot p is
+        pixel p); round 0 renders {p, 0, min_samples}, then each round refines the list on the
+        device (rt_refine_jobs), reads the 16 bytes of stats back and renders what is left with
+        accumulate, until no job goes on.  -> (sums (H, W, 3), sumsq (H, W, 3), n int32 (H, W) --
+        device tensors -- and the number of rendering rounds)."""
+        import torch
+        W, H = cam.image_width, cam.image_height
+        npx = W * H
+        params = RtAdaptiveParams(rel_error, abs_floor, min_samples, max_samples,
+                                  max_samples if max_step is None else max_step, 0)
+        tdt = torch.from_numpy(np.zeros(0, self.dtype)).dtype
+        jobs = np.zeros(npx, RtPixelJob)
+        jobs["pixel"], jobs["sample_count"] = np.arange(npx), min_samples
+        d_jobs = torch.from_numpy(jobs.view(np.int32).reshape(npx, 4)).to("cuda")
+        d_sums = torch.empty((H, W, 3), dtype=tdt, device="cuda")
+        d_sq = torch.empty((H, W, 3), dtype=tdt, device="cuda")
+        d_stats = torch.zeros(2, dtype=torch.int64, device="cuda")
+        stream = torch.cuda.current_stream().cuda_stream
+        # (torch's null stream reaches the library as "the context's own stream", which torch's copies
+        # are not ordered with: wait for the device before the first call and before every read-back)
+        torch.cuda.synchronize()
+        rounds = 0
+        while True:
+            self.render_pixels_moments(cam, d_jobs.data_ptr(), npx, max_depth, d_sums.data_ptr(), d_sq.data_ptr(),
+                                       None, rounds > 0, stream)
+            rounds += 1
+            self.refine_jobs(d_jobs.data_ptr(), npx, d_sums.data_ptr(), d_sq.data_ptr(), params, d_stats.data_ptr(),
+                             stream)
+            torch.cuda.synchronize()
+            if int(d_stats.cpu()[0]) == 0:
+                break
+        return d_sums, d_sq, d_jobs[:, 1].contiguous().view(H, W), rounds
 
     @staticmethod
     def _jobs(jobs) -> np.ndarray:

@@ -325,6 +325,23 @@ class camera:
         jobs["sample_count"] = self.samples_per_pixel if sample_count is None else sample_count
         return self._renderer.render_pixels_host(self._cam, jobs, self.max_depth)
 
+    def render_adaptive(self, world: hittable, rel_error: float, abs_floor: float = 0.0, min_samples: int = 16,
+                        max_samples: int | None = None, max_step: int | None = None):
+        """The frame with a per-pixel sample count (Renderer.render_adaptive: rt_render_pixels_moments
+        and rt_refine_jobs in rounds): every pixel takes samples 0, 1, ... of its own stream until the
+        standard error of its mean is within rel_error of max(|mean|, abs_floor), between min_samples
+        and max_samples (default: samples_per_pixel).  -> (mean[H, W, 3] = sums / n in the camera's
+        precision, n int32[H, W]); rt_quantize(mean, spp = 1) quantises the mean."""
+        self.initialize()
+        if self._renderer is None:
+            self._renderer = N.Renderer(self.device, self.seed, self.precision)
+        self._upload(self._renderer, world)
+        hi = self.samples_per_pixel if max_samples is None else max_samples
+        sums, _, n, _ = self._renderer.render_adaptive(self._cam, self.max_depth, rel_error, abs_floor,
+                                                       min(min_samples, hi), hi, max_step)
+        sums, n = sums.cpu().numpy(), n.cpu().numpy()
+        return sums / n[..., None].astype(sums.dtype), n
+
 
 def write_ppm(out, rgb: np.ndarray) -> None:
     """PPM P3 exactly as camera.h:35 and color.h:32-34 print it."""

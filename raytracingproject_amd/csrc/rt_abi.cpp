@@ -262,6 +262,8 @@ void rt_destroy(rt_ctx* c) {
     (void)hipFree(c->d_px_flags);
     (void)hipFree(c->d_px_samples);
     (void)hipFree(c->d_px_sseg);
+    (void)hipFree(c->d_px_sq);
+    (void)hipFree(c->d_px_sqflags);
     (void)hipFree(c->d_gather);
     for (auto& a : c->accum) {
         (void)hipFree(a.acc);
@@ -333,7 +335,9 @@ int rt_set_tuning(rt_ctx* c, const rt_tuning* t) {
         return fail(c, RT_ERR_INVALID, "mesh_lds_nodes %d (-1 = auto, 0..%d)", t->mesh_lds_nodes, MESH_TOP_MAX);
     if (!(t->mesh_cost_traverse > 0)) return fail(c, RT_ERR_INVALID, "mesh_cost_traverse must be > 0");
     if (t->chunk_waves < 0) return fail(c, RT_ERR_INVALID, "chunk_waves %d (0 = off)", t->chunk_waves);
-    if (t->sample_buffer_mb < 16) return fail(c, RT_ERR_INVALID, "sample_buffer_mb %d (>= 16)", t->sample_buffer_mb);
+    // (>= 16 until rt_render_pixels_moments: a 1 MiB pass, 37,449 samples of a job list, lets a test cross a
+    // pass boundary with a small list; rt_render's passes hold at least one sample per pixel whatever the cap)
+    if (t->sample_buffer_mb < 1) return fail(c, RT_ERR_INVALID, "sample_buffer_mb %d (>= 1)", t->sample_buffer_mb);
     if (t->mesh_block != 0 && t->mesh_block != 256 && t->mesh_block != 512 && t->mesh_block != 768)
         return fail(c, RT_ERR_INVALID, "mesh_block %d (0 = auto, 256, 512 or 768)", t->mesh_block);
     if (t->mesh_lds_stack < -1 || t->mesh_lds_stack > MESH_STACK_MAX)
@@ -1155,21 +1159,24 @@ int rt_camera_rays(rt_ctx* c, const rt_camera* cam, const rt_pixel_job* jobs, in
     return RT_OK;
 }
 
-int rt_render_pixels(rt_ctx* c, const rt_camera* cam, const rt_pixel_job* jobs, int num_jobs, int max_depth,
-                     int accumulate, void* out_sums, uint32_t* out_segments, void* stream) {
+// rt_render_pixels, and with `moments` rt_render_pixels_moments: the same launches, the second
+// moment's siblings (csrc/rt_moments.h) in place of the path kernel (fp32) or the reduction (fp64).
+static int render_pixels(rt_ctx* c, const char* what, const rt_camera* cam, const rt_pixel_job* jobs, int num_jobs,
+                         int max_depth, int accumulate, void* out_sums, bool moments, void* out_sumsq,
+                         uint32_t* out_segments, void* stream) {
     if (!c) return RT_ERR_INVALID;
-    if (!c->has_scene) return fail(c, RT_ERR_NO_SCENE, "rt_render_pixels before rt_upload_scene");
+    if (!c->has_scene) return fail(c, RT_ERR_NO_SCENE, "%s before rt_upload_scene", what);
     int rc = check_camera(c, cam);
     if (rc) return rc;
-    if (num_jobs < 0 || (num_jobs > 0 && (!jobs || !out_sums)))
-        return fail(c, RT_ERR_INVALID, "rt_render_pixels: %d jobs, jobs %p, out_sums %p", num_jobs, (const void*)jobs,
-                    out_sums);
+    if (num_jobs < 0 || (num_jobs > 0 && (!jobs || !out_sums || (moments && !out_sumsq))))
+        return fail(c, RT_ERR_INVALID, "%s: %d jobs, jobs %p, out_sums %p, out_sumsq %p", what, num_jobs,
+                    (const void*)jobs, out_sums, out_sumsq);
     const bool f64 = c->precision == RT_PREC_F64;
     if (f64 && max_depth > 64)
         return fail(c, RT_ERR_LIMIT, "fp64 path keeps at most 64 bounces (max_depth %d)", max_depth);
     RenderParams P;
     size_t lds;
-    if ((rc = query_setup(c, "rt_render_pixels", P, lds, cam))) return rc;
+    if ((rc = query_setup(c, what, P, lds, cam))) return rc;
     if (num_jobs == 0) return RT_OK;
     P.max_depth = max_depth;
     const size_t nj = (size_t)num_jobs;
@@ -1181,25 +1188,39 @@ int rt_render_pixels(rt_ctx* c, const rt_camera* cam, const rt_pixel_job* jobs, 
     if (max_depth <= 0) {   // camera_cpu.h:9-10: no path, no light; accumulate: nothing to add
         if (!accumulate) {
             e = hipMemsetAsync(out_sums, 0, nj * 3 * elem_bytes(c), st);
+            if (e == hipSuccess && moments) e = hipMemsetAsync(out_sumsq, 0, nj * 3 * elem_bytes(c), st);
             if (e == hipSuccess && out_segments) e = hipMemsetAsync(out_segments, 0, nj * sizeof(uint32_t), st);
         }
     } else {
         unsigned long long total = 0;
         if ((rc = pixel_scan(c, cam, jobs, num_jobs, st, total))) return rc;
-        if (total > 0x7fffffffull) return fail(c, RT_ERR_LIMIT, "rt_render_pixels: %llu samples (> 2^31 - 1)", total);
+        if (total > 0x7fffffffull) return fail(c, RT_ERR_LIMIT, "%s: %llu samples (> 2^31 - 1)", what, total);
         const unsigned long long* off = c->d_px_offsets;
         if (!f64) {
             if ((rc = grow(c, (void**)&c->d_px_acc, &c->px_acc_cap, nj * 3 * sizeof(long long)))) return rc;
             if ((rc = grow(c, (void**)&c->d_px_flags, &c->px_flags_cap, nj * sizeof(uint32_t)))) return rc;
+            if (moments) {
+                if ((rc = grow(c, (void**)&c->d_px_sq, &c->px_sq_cap, nj * 6 * sizeof(unsigned long long)))) return rc;
+                if ((rc = grow(c, (void**)&c->d_px_sqflags, &c->px_sqflags_cap, nj * sizeof(uint32_t)))) return rc;
+            }
             e = launch_pixels_seed(off, num_jobs, accumulate ? 1 : 0, (const float*)out_sums, c->d_px_acc, c->d_px_flags,
                                    out_segments, st);
+            if (e == hipSuccess && moments)
+                e = launch_pixels_seed_moments(off, num_jobs, accumulate ? 1 : 0, (const float*)out_sumsq, c->d_px_sq,
+                                               c->d_px_sqflags, st);
             if (e == hipSuccess) e = hipMemsetAsync(c->d_queue_px, 0, QUEUE_CTRL_BYTES, st);
             if (e == hipSuccess)
-                e = launch_pixels_f32(P, lds, st, jobs, off, num_jobs, total, 0, (int)total, (unsigned long long*)c->d_px_acc,
-                                      c->d_px_flags, out_segments, c->n_cu);
+                e = moments ? launch_pixels_moments_f32(P, lds, st, jobs, off, num_jobs, total, 0, (int)total,
+                                                        (unsigned long long*)c->d_px_acc, c->d_px_flags, out_segments,
+                                                        c->d_px_sq, c->d_px_sqflags, c->n_cu, c->tuning.grid_workgroups)
+                            : launch_pixels_f32(P, lds, st, jobs, off, num_jobs, total, 0, (int)total,
+                                                (unsigned long long*)c->d_px_acc, c->d_px_flags, out_segments, c->n_cu);
             if (e == hipSuccess)
                 e = launch_pixels_finalize(off, num_jobs, accumulate ? 1 : 0, c->d_px_acc, c->d_px_flags,
                                            (float*)out_sums, st);
+            if (e == hipSuccess && moments)
+                e = launch_pixels_finalize_moments(off, num_jobs, accumulate ? 1 : 0, c->d_px_sq, c->d_px_sqflags,
+                                                   (float*)out_sumsq, st);
         } else {
             // passes of at most floor(sample_buffer_mb 2^20 / 28) samples, reduced in order; the
             // first one also zeroes the jobs without samples, so it runs even when T = 0
@@ -1213,15 +1234,58 @@ int rt_render_pixels(rt_ctx* c, const rt_camera* cam, const rt_pixel_job* jobs, 
                 e = hipMemsetAsync(c->d_queue_px, 0, QUEUE_CTRL_BYTES, st);
                 if (e == hipSuccess)
                     e = launch_pixels_f64(P, lds, st, jobs, off, num_jobs, total, q0, (int)(q1 - q0), c->d_px_samples,
-                                          c->d_px_sseg, c->n_cu);
+                                          c->d_px_sseg, c->n_cu, moments ? c->tuning.grid_workgroups : 0);
                 if (e == hipSuccess)
-                    e = launch_pixels_reduce(off, num_jobs, q0, q1, c->d_px_samples, c->d_px_sseg, accumulate ? 1 : 0,
-                                             (double*)out_sums, out_segments, st);
+                    e = moments ? launch_pixels_reduce_moments(off, num_jobs, q0, q1, c->d_px_samples, c->d_px_sseg,
+                                                               accumulate ? 1 : 0, (double*)out_sums,
+                                                               (double*)out_sumsq, out_segments, st)
+                                : launch_pixels_reduce(off, num_jobs, q0, q1, c->d_px_samples, c->d_px_sseg,
+                                                       accumulate ? 1 : 0, (double*)out_sums, out_segments, st);
                 q0 = q1;
             } while (q0 < total && e == hipSuccess);
         }
     }
     if (e != hipSuccess) return fail(c, RT_ERR_HIP, "pixel render launch: %s", hipGetErrorString(e));
+    HIPCHK(c, hipEventRecord(c->ev1, st));
+    c->timed = true;
+    return RT_OK;
+}
+
+int rt_render_pixels(rt_ctx* c, const rt_camera* cam, const rt_pixel_job* jobs, int num_jobs, int max_depth,
+                     int accumulate, void* out_sums, uint32_t* out_segments, void* stream) {
+    return render_pixels(c, "rt_render_pixels", cam, jobs, num_jobs, max_depth, accumulate, out_sums, false, nullptr,
+                         out_segments, stream);
+}
+
+int rt_render_pixels_moments(rt_ctx* c, const rt_camera* cam, const rt_pixel_job* jobs, int num_jobs, int max_depth,
+                             int accumulate, void* out_sums, void* out_sumsq, uint32_t* out_segments, void* stream) {
+    return render_pixels(c, "rt_render_pixels_moments", cam, jobs, num_jobs, max_depth, accumulate, out_sums, true,
+                         out_sumsq, out_segments, stream);
+}
+
+int rt_refine_jobs(rt_ctx* c, rt_pixel_job* jobs, int num_jobs, const void* sums, const void* sumsq,
+                   const rt_adaptive_params* ap, uint64_t* stats, void* stream) {
+    if (!c) return RT_ERR_INVALID;
+    if (num_jobs < 0 || (num_jobs > 0 && (!jobs || !sums || !sumsq || !ap || !stats)))
+        return fail(c, RT_ERR_INVALID, "rt_refine_jobs: %d jobs, jobs %p, sums %p, sumsq %p, params %p, stats %p",
+                    num_jobs, (void*)jobs, sums, sumsq, (const void*)ap, (void*)stats);
+    if (ap && (ap->min_samples < 2 || ap->min_samples > ap->max_samples || ap->max_samples > 0x7fffffffu ||
+               ap->max_step == 0))
+        return fail(c, RT_ERR_INVALID, "rt_refine_jobs: 2 <= min_samples %u <= max_samples %u <= 2^31 - 1, max_step %u >= 1",
+                    ap->min_samples, ap->max_samples, ap->max_step);
+    if (ap && !(std::isfinite(ap->rel_error) && ap->rel_error >= 0.0 && std::isfinite(ap->abs_floor) &&
+                ap->abs_floor >= 0.0))
+        return fail(c, RT_ERR_INVALID, "rt_refine_jobs: rel_error %g and abs_floor %g must be finite and >= 0",
+                    ap->rel_error, ap->abs_floor);
+    if (!stats) return RT_OK;   // (no jobs, nothing to count)
+    HIPCHK(c, hipSetDevice(c->device));
+    hipStream_t st = stream ? (hipStream_t)stream : c->stream;
+    HIPCHK(c, hipEventRecord(c->ev0, st));
+    hipError_t e = hipMemsetAsync(stats, 0, 2 * sizeof(uint64_t), st);
+    if (e == hipSuccess && num_jobs > 0)
+        e = launch_refine_jobs(jobs, num_jobs, sums, sumsq, (int)elem_bytes(c), ap->rel_error, ap->abs_floor,
+                               ap->min_samples, ap->max_samples, ap->max_step, (unsigned long long*)stats, st);
+    if (e != hipSuccess) return fail(c, RT_ERR_HIP, "refine launch: %s", hipGetErrorString(e));
     HIPCHK(c, hipEventRecord(c->ev1, st));
     c->timed = true;
     return RT_OK;

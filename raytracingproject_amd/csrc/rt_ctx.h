@@ -101,6 +101,12 @@ struct rt_ctx {
     size_t px_samples_cap = 0;
     uint32_t* d_px_sseg = nullptr;
     size_t px_sseg_cap = 0;
+    // rt_render_pixels_moments, fp32: the second moments' two words per job and channel
+    // (num_jobs x 6) and their flags
+    unsigned long long* d_px_sq = nullptr;
+    size_t px_sq_cap = 0;
+    uint32_t* d_px_sqflags = nullptr;
+    size_t px_sqflags_cap = 0;
     void* d_gather = nullptr;  // rt_render_frame_multi: all contexts' shards
     size_t gather_cap = 0;
 

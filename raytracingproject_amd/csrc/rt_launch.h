@@ -87,7 +87,7 @@ hipError_t launch_pixels_f32(const RenderParams& P, size_t lds_bytes, hipStream_
 hipError_t launch_pixels_f64(const RenderParams& P, size_t lds_bytes, hipStream_t stream, const void* jobs,
                              const unsigned long long* offsets, int num_jobs, unsigned long long total,
                              unsigned long long q_begin, int n,
-                             double* samples, uint32_t* sample_segs, int n_cu);
+                             double* samples, uint32_t* sample_segs, int n_cu, int max_wgs = 0);
 // fp64: one pass's samples [q_begin, q_end) into out_sums / out_segments (may be null), per job
 // in sample order (pixels_reduce_kernel)
 hipError_t launch_pixels_reduce(const unsigned long long* offsets, int num_jobs, unsigned long long q_begin,
@@ -100,6 +100,32 @@ hipError_t launch_pixels_seed(const unsigned long long* offsets, int num_jobs, i
                               long long* acc, uint32_t* flags, uint32_t* out_segments, hipStream_t stream);
 hipError_t launch_pixels_finalize(const unsigned long long* offsets, int num_jobs, int accumulate,
                                   const long long* acc, const uint32_t* flags, float* out_sums, hipStream_t stream);
+// rt_render_pixels_moments (csrc/rt_moments.h): the launches above with the per-job second
+// moment.  fp32: sq (num_jobs x 3 x 2 words: the low and high 32-bit halves of the squares,
+// summed, in units of 2^-38) and sqflags (num_jobs) beside acc and flags, seeded from and
+// finalized into out_sumsq; fp64: the reduction continues out_sumsq as it continues out_sums.
+// max_wgs > 0 (rt_tuning.grid_workgroups) caps the path kernel's grid, here and in
+// launch_pixels_f64.
+hipError_t launch_pixels_moments_f32(const RenderParams& P, size_t lds_bytes, hipStream_t stream, const void* jobs,
+                                     const unsigned long long* offsets, int num_jobs, unsigned long long total,
+                                     unsigned long long q_begin, int n, unsigned long long* acc, uint32_t* flags,
+                                     uint32_t* segments, unsigned long long* sq, uint32_t* sqflags, int n_cu,
+                                     int max_wgs);
+hipError_t launch_pixels_reduce_moments(const unsigned long long* offsets, int num_jobs, unsigned long long q_begin,
+                                        unsigned long long q_end, const double* samples, const uint32_t* sample_segs,
+                                        int accumulate, double* out_sums, double* out_sumsq, uint32_t* out_segments,
+                                        hipStream_t stream);
+hipError_t launch_pixels_seed_moments(const unsigned long long* offsets, int num_jobs, int accumulate,
+                                      const float* out_sumsq, unsigned long long* sq, uint32_t* sqflags,
+                                      hipStream_t stream);
+hipError_t launch_pixels_finalize_moments(const unsigned long long* offsets, int num_jobs, int accumulate,
+                                          const unsigned long long* sq, const uint32_t* sqflags, float* out_sumsq,
+                                          hipStream_t stream);
+// rt_refine_jobs: jobs (rt_pixel_job, device) rewritten in place from sums / sumsq (num_jobs x 3
+// of elem_bytes 4 or 8) by rt_adaptive_params' fields; stats: two words, added to
+hipError_t launch_refine_jobs(void* jobs, int num_jobs, const void* sums, const void* sumsq, int elem_bytes,
+                              double rel_error, double abs_floor, uint32_t min_samples, uint32_t max_samples,
+                              uint32_t max_step, unsigned long long* stats, hipStream_t stream);
 hipError_t launch_tape_f64(const RenderParams& P, int max_depth, const double* ray7, const double* tape, int tape_len,
                            double* out, int* used, hipStream_t stream);
 // element: 4 (float/uint32) or 8 (double); channels: 1 or 3

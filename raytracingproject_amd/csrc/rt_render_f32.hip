@@ -7,6 +7,7 @@
 #include "rt_occluded.h"   // (includes rt_render_impl.h)
 #include "rt_radiance.h"
 #include "rt_pixels.h"
+#include "rt_moments.h"
 
 namespace rtx {
 
@@ -185,6 +186,31 @@ hipError_t launch_pixels_f32(const RenderParams& P, size_t lds_bytes, hipStream_
         static const int v = radiance_vgprs((const void*)kern);
         hipLaunchKernelGGL(kern, dim3(radiance_grid<B>(v, lds_bytes, n, n_cu)), dim3(B), lds_bytes, stream, P, j,
                            offsets, num_jobs, total, q_begin, n, acc, flags, segments, (float*)nullptr, (uint32_t*)nullptr);
+    }
+    return hipGetLastError();
+}
+
+// rt_render_pixels_moments, fp32: launch_pixels_f32's flags, register budgets and grid.
+hipError_t launch_pixels_moments_f32(const RenderParams& P, size_t lds_bytes, hipStream_t stream, const void* jobs,
+                                     const unsigned long long* offsets, int num_jobs, unsigned long long total,
+                                     unsigned long long q_begin, int n, unsigned long long* acc, uint32_t* flags,
+                                     uint32_t* segments, unsigned long long* sq, uint32_t* sqflags, int n_cu,
+                                     int max_wgs) {
+    if (n <= 0) return hipSuccess;
+    constexpr int B = TRACE_BLOCK;
+    constexpr int TS = TRAV_SELROOT | TRAV_B128 | TRAV_CULL, TM = TRAV_SELROOT | TRAV_CULL | TRAV_MIFIF;
+    const PixelJob* j = (const PixelJob*)jobs;
+    const auto cap = [max_wgs](int g) { return max_wgs > 0 && g > max_wgs ? max_wgs : g; };
+    if (P.n_mnodes > 0) {
+        auto* kern = pixels_moments_kernel<B, RADIANCE_MESH_WPE, TM, true>;
+        static const int v = radiance_vgprs((const void*)kern);
+        hipLaunchKernelGGL(kern, dim3(cap(radiance_grid<B>(v, lds_bytes, n, n_cu))), dim3(B), lds_bytes, stream, P, j,
+                           offsets, num_jobs, total, q_begin, n, acc, flags, segments, sq, sqflags);
+    } else {
+        auto* kern = pixels_moments_kernel<B, RADIANCE_WPE, TS, false>;
+        static const int v = radiance_vgprs((const void*)kern);
+        hipLaunchKernelGGL(kern, dim3(cap(radiance_grid<B>(v, lds_bytes, n, n_cu))), dim3(B), lds_bytes, stream, P, j,
+                           offsets, num_jobs, total, q_begin, n, acc, flags, segments, sq, sqflags);
     }
     return hipGetLastError();
 }

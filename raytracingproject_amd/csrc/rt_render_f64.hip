@@ -4,6 +4,7 @@
 #include "rt_occluded.h"   // (includes rt_render_impl.h)
 #include "rt_radiance.h"
 #include "rt_pixels.h"
+#include "rt_moments.h"
 
 #include <hipcub/hipcub.hpp>
 
@@ -331,20 +332,21 @@ hipError_t launch_camera_rays_f64(const RenderParams& P, hipStream_t stream, con
 hipError_t launch_pixels_f64(const RenderParams& P, size_t lds_bytes, hipStream_t stream, const void* jobs,
                              const unsigned long long* offsets, int num_jobs, unsigned long long total,
                              unsigned long long q_begin, int n,
-                             double* samples, uint32_t* sample_segs, int n_cu) {
+                             double* samples, uint32_t* sample_segs, int n_cu, int max_wgs) {
     if (n <= 0) return hipSuccess;
     constexpr int B = TRACE_BLOCK;
     const PixelJob* j = (const PixelJob*)jobs;
+    const auto cap = [max_wgs](int g) { return max_wgs > 0 && g > max_wgs ? max_wgs : g; };
     if (P.n_mnodes > 0) {
         auto* kern = pixels_kernel<double, true, B, 4, TRAV_F32BOX, true>;
         static const int v = radiance_vgprs((const void*)kern);
-        hipLaunchKernelGGL(kern, dim3(radiance_grid<B>(v, lds_bytes, n, n_cu)), dim3(B), lds_bytes, stream, P, j,
+        hipLaunchKernelGGL(kern, dim3(cap(radiance_grid<B>(v, lds_bytes, n, n_cu))), dim3(B), lds_bytes, stream, P, j,
                            offsets, num_jobs, total, q_begin, n, (unsigned long long*)nullptr, (uint32_t*)nullptr,
                            (uint32_t*)nullptr, samples, sample_segs);
     } else {
         auto* kern = pixels_kernel<double, true, B, 4, TRAV_F32BOX, false>;
         static const int v = radiance_vgprs((const void*)kern);
-        hipLaunchKernelGGL(kern, dim3(radiance_grid<B>(v, lds_bytes, n, n_cu)), dim3(B), lds_bytes, stream, P, j,
+        hipLaunchKernelGGL(kern, dim3(cap(radiance_grid<B>(v, lds_bytes, n, n_cu))), dim3(B), lds_bytes, stream, P, j,
                            offsets, num_jobs, total, q_begin, n, (unsigned long long*)nullptr, (uint32_t*)nullptr,
                            (uint32_t*)nullptr, samples, sample_segs);
     }
@@ -408,6 +410,104 @@ hipError_t launch_pixels_finalize(const unsigned long long* offsets, int num_job
     if (num_jobs <= 0) return hipSuccess;
     hipLaunchKernelGGL(px_finalize_kernel, dim3((unsigned)((num_jobs + 255) / 256)), dim3(256), 0, stream, offsets,
                        num_jobs, accumulate, acc, flags, out_sums);
+    return hipGetLastError();
+}
+
+// ---- second moments and refinement (rt_render_pixels_moments, rt_refine_jobs; rt_moments.h) ----
+hipError_t launch_pixels_reduce_moments(const unsigned long long* offsets, int num_jobs, unsigned long long q_begin,
+                                        unsigned long long q_end, const double* samples, const uint32_t* sample_segs,
+                                        int accumulate, double* out_sums, double* out_sumsq, uint32_t* out_segments,
+                                        hipStream_t stream) {
+    if (num_jobs <= 0) return hipSuccess;
+    hipLaunchKernelGGL(pixels_reduce_moments_kernel<double>, dim3((unsigned)((num_jobs + 255) / 256)), dim3(256), 0,
+                       stream, offsets, num_jobs, q_begin, q_end, samples, sample_segs, accumulate, out_sums, out_sumsq,
+                       out_segments);
+    return hipGetLastError();
+}
+
+// fp32, one thread per job, before the path kernel: the second moment's two words start at 0,
+// or (accumulate, a job that has samples) at X = rint((double)out_sq 2^38) for 0 <= out_sq <
+// 2^57 -- high word X >> 32, low word X & 0xffffffff; a negative or NaN start is SQ_NAN, one of
+// 2^57 or more SQ_INF.
+__global__ void px_seed_moments_kernel(const unsigned long long* __restrict__ offsets, int num_jobs, int accumulate,
+                                       const float* __restrict__ out_sq, unsigned long long* __restrict__ sq,
+                                       uint32_t* __restrict__ sqflags) {
+    const int k = blockIdx.x * blockDim.x + threadIdx.x;
+    if (k >= num_jobs) return;
+    uint32_t fl = 0;
+    const bool cont = accumulate && offsets[k] != offsets[k + 1];
+    for (int c = 0; c < 3; ++c) {
+        unsigned long long lo = 0, hi = 0;
+        if (cont) {
+            const double s = (double)out_sq[(size_t)k * 3 + c];
+            if (s != s || s < 0.0) {
+                fl |= SQ_NAN << (2 * c);
+            } else if (s >= 0x1p57) {
+                fl |= SQ_INF << (2 * c);
+            } else {   // X < 2^95: its halves are exact in doubles
+                const double X = rint(dmul_rn(s, 0x1p38)), h = floor(dmul_rn(X, 0x1p-32));
+                hi = (unsigned long long)h;
+                lo = (unsigned long long)dsub_rn(X, dmul_rn(h, 0x1p32));
+            }
+        }
+        sq[((size_t)k * 3 + c) * 2] = lo;
+        sq[((size_t)k * 3 + c) * 2 + 1] = hi;
+    }
+    sqflags[k] = fl;
+}
+
+// ... and after it: out_sq = (float)(((double)high 2^32 + (double)low) 2^-38), NaN or +inf for
+// a flagged channel (NaN wins); with accumulate a job without samples keeps what out_sq holds.
+__global__ void px_finalize_moments_kernel(const unsigned long long* __restrict__ offsets, int num_jobs,
+                                           int accumulate, const unsigned long long* __restrict__ sq,
+                                           const uint32_t* __restrict__ sqflags, float* __restrict__ out_sq) {
+    const int k = blockIdx.x * blockDim.x + threadIdx.x;
+    if (k >= num_jobs) return;
+    if (accumulate && offsets[k] == offsets[k + 1]) return;
+    for (int c = 0; c < 3; ++c) {
+        const uint32_t f = (sqflags[k] >> (2 * c)) & 3u;
+        const unsigned long long lo = sq[((size_t)k * 3 + c) * 2], hi = sq[((size_t)k * 3 + c) * 2 + 1];
+        float v;
+        if (f & SQ_NAN)
+            v = __builtin_nanf("");
+        else if (f)
+            v = __builtin_huge_valf();
+        else
+            v = (float)dmul_rn(dmul_rn((double)hi, 0x1p32) + (double)lo, 0x1p-38);
+        out_sq[(size_t)k * 3 + c] = v;
+    }
+}
+
+hipError_t launch_pixels_seed_moments(const unsigned long long* offsets, int num_jobs, int accumulate,
+                                      const float* out_sumsq, unsigned long long* sq, uint32_t* sqflags,
+                                      hipStream_t stream) {
+    if (num_jobs <= 0) return hipSuccess;
+    hipLaunchKernelGGL(px_seed_moments_kernel, dim3((unsigned)((num_jobs + 255) / 256)), dim3(256), 0, stream, offsets,
+                       num_jobs, accumulate, out_sumsq, sq, sqflags);
+    return hipGetLastError();
+}
+
+hipError_t launch_pixels_finalize_moments(const unsigned long long* offsets, int num_jobs, int accumulate,
+                                          const unsigned long long* sq, const uint32_t* sqflags, float* out_sumsq,
+                                          hipStream_t stream) {
+    if (num_jobs <= 0) return hipSuccess;
+    hipLaunchKernelGGL(px_finalize_moments_kernel, dim3((unsigned)((num_jobs + 255) / 256)), dim3(256), 0, stream,
+                       offsets, num_jobs, accumulate, sq, sqflags, out_sumsq);
+    return hipGetLastError();
+}
+
+hipError_t launch_refine_jobs(void* jobs, int num_jobs, const void* sums, const void* sumsq, int elem_bytes,
+                              double rel_error, double abs_floor, uint32_t min_samples, uint32_t max_samples,
+                              uint32_t max_step, unsigned long long* stats, hipStream_t stream) {
+    if (num_jobs <= 0) return hipSuccess;
+    const AdaptiveParams A{rel_error, abs_floor, min_samples, max_samples, max_step, 0u};
+    const dim3 grid((unsigned)((num_jobs + 255) / 256)), block(256);
+    if (elem_bytes == 8)
+        hipLaunchKernelGGL(refine_jobs_kernel<double>, grid, block, 0, stream, (PixelJob*)jobs, num_jobs,
+                           (const double*)sums, (const double*)sumsq, A, stats);
+    else
+        hipLaunchKernelGGL(refine_jobs_kernel<float>, grid, block, 0, stream, (PixelJob*)jobs, num_jobs,
+                           (const float*)sums, (const float*)sumsq, A, stats);
     return hipGetLastError();
 }
 
