@@ -646,8 +646,12 @@ int rt_render_diag(rt_ctx* ctx, const rt_camera* cam, int samples_per_pixel, int
  * RT_BATCH_ADOPT in INTEGRATION.md; never queued, so not in slot 15).  31: grid walks
  * suspended (the sphere-only kernel over the flat grid walk, see RT_GRID_SUSPEND in
  * INTEGRATION.md; 0 for every other kernel); a resumed walk counts no new world.hit call in
- * slot 10, though its trace counts in slots 0 and 1. */
-enum { RT_DIAG_SLOTS = 32 };
+ * slot 10, though its trace counts in slots 0 and 1.  32-39 (the same sphere-only grid kernels;
+ * 0 for every other kernel): the pop passes of slot 27 by the number of lanes that popped in
+ * the pass -- 32: 1-2 lanes, 33: 3-6, 34: 7-16, 35: more than 16, for passes that do not
+ * directly follow a batch in which a lane adopted its hit; 36-39: the same four buckets for
+ * passes that directly follow such a batch in the same shade round.  The eight sum to slot 27. */
+enum { RT_DIAG_SLOTS = 40 };
 int rt_render_diag_ex(rt_ctx* ctx, const rt_camera* cam, int samples_per_pixel, int max_depth, uint64_t* counters,
                       int n);
 

@@ -23,7 +23,7 @@ RT_TRAV_GRID = 65536   # fp32 sphere scenes: the uniform sphere grid (ABI 8)
 RT_TRAV_GFLAT, RT_TRAV_G3D = 131072, 262144   # its flat walk (added by the library), keep the 3-D walk (ABI 11)
 # (RT_TRAV_TBIN and RT_TRAV_MTOP: removed in ABI 6, refused by rt_set_tuning)
 RT_TRAV_DEFAULT = RT_TRAV_COH | RT_TRAV_SELROOT | RT_TRAV_B128 | RT_TRAV_CULL | RT_TRAV_GRID
-RT_DIAG_SLOTS = 32   # rt_hip.h: counters of rt_render_diag_ex
+RT_DIAG_SLOTS = 40  # rt_hip.h: counters of rt_render_diag_ex
 RT_COMM_ID_BYTES = 128
 RT_LAMBERTIAN, RT_METAL, RT_DIELECTRIC = 0, 1, 2
 RT_PREC_F32, RT_PREC_F64 = 0, 1
@@ -477,6 +477,11 @@ class Renderer:
         grid = self.precision == RT_PREC_F32 and i.num_triangles == 0 and bool(i.render_traversal & RT_TRAV_GRID)
         d.update(pop_passes=d["mnode_it"] if grid else None, pop_lanes=d["mnode_act"] if grid else None,
                  hits_adopted=d["mtri_it"] if grid else None)
+        # slots 32-39, the same kernels: the pop passes by the lanes that popped in them (1-2, 3-6,
+        # 7-16, more than 16), first the passes that do not directly follow an adopting batch,
+        # then those that do
+        hist = [int(c[k]) for k in range(32, 40)]
+        d.update(pop_pass_hist=hist[:4] if grid else None, pop_pass_hist_after_adopt=hist[4:] if grid else None)
         return d
 
     def trace_rays(self, rays_dev: int, n: int, hits_dev: int, stream: int | None = None) -> None:

@@ -225,7 +225,7 @@ constexpr int FIX_ITEM_SAMPLES = 32;         // <= 32 such values in [0, 1] sum 
 constexpr int FIX_LAUNCH_SAMPLES = 8191;     // a launch's packed sums stay below 2^32 per channel
 // accum_flags bits, per channel c at bit 3c: NaN, +overflow (+inf), -overflow (-inf)
 constexpr uint32_t FIX_NAN = 1u, FIX_POS = 2u, FIX_NEG = 4u;
-constexpr int DIAG_SLOTS = 32;   // rt_render_diag_ex (RT_DIAG_SLOTS)
+constexpr int DIAG_SLOTS = 40;   // rt_render_diag_ex (RT_DIAG_SLOTS)
 
 // Coherent primaries (TRAV_COH, render_coherent): per wave, a FIFO of primary hits that
 // wait for a lane to shade them, then the current work item's pixel sums (64 x 3 floats).
@@ -262,9 +262,29 @@ struct CohEntryD<true> {
     uint32_t pad;
 };
 static_assert(sizeof(CohEntryD<false>) == 16 && sizeof(CohEntryD<true>) == 24, "CohEntryD");
-template <class R, bool MESH> struct CohEntrySel { using type = CohEntryT<MESH>; };
-template <bool MESH> struct CohEntrySel<double, MESH> { using type = CohEntryD<MESH>; };
-template <class R, bool MESH> using CohEntryX = typename CohEntrySel<R, MESH>::type;
+// Compile-time switches of r13's two parts, for same-box A/Bs of each alone
+// (tools/build_variant.sh NAME "-DRT_FIFO_RNG0=0" / "-DRT_CAM_ONEBASE=0"; DESIGN.md section 5 "Round 13")
+#ifndef RT_FIFO_RNG0
+#define RT_FIFO_RNG0 1
+#endif
+#ifndef RT_CAM_ONEBASE
+#define RT_CAM_ONEBASE 1
+#endif
+// r13, the fp32 sphere-grid kernels (coh_rng0): the entry also carries the path's RNG state
+// right after CounterRng::start, as the batch computed it, so that the pop sets it instead of
+// hashing pixel and sample again.  One 16-byte LDS write and one 16-byte LDS read per entry.
+struct alignas(16) CohEntryR {
+    float t;
+    uint32_t pix;
+    uint32_t sid;    // as CohEntryT<false>
+    uint32_t rng0;   // CounterRng::st after start(pixel key, sample)
+};
+static_assert(sizeof(CohEntryR) == 16 && alignof(CohEntryR) == 16, "CohEntryR");
+template <class R, bool MESH, bool RNG0> struct CohEntrySel { using type = CohEntryT<MESH>; };
+template <bool MESH, bool RNG0> struct CohEntrySel<double, MESH, RNG0> { using type = CohEntryD<MESH>; };
+template <> struct CohEntrySel<float, false, true> { using type = CohEntryR; };
+// (RNG0: coh_rng0 of the kernel)
+template <class R, bool MESH, bool RNG0 = false> using CohEntryX = typename CohEntrySel<R, MESH, RNG0>::type;
 constexpr size_t COH_SUM_BYTES = 64 * 3 * sizeof(float);   // the wave's item pixel sums
 // each lane's path throughput and scatter count, parked in LDS across the trace by the fp32
 // mixed-scene kernels (coh_parks)
@@ -273,8 +293,11 @@ constexpr size_t COH_PARK_BYTES = 64 * 4 * sizeof(float);
 // sums, then (coh_parks) the parked path state, then (coh_cands) the item's candidate list
 constexpr size_t coh_wave_bytes(bool mesh, bool sums, int fifo = COH_FIFO, bool f64 = false, bool park = false,
                                 bool cand = false) {
-    return (size_t)fifo * (f64 ? (mesh ? sizeof(CohEntryD<true>) : sizeof(CohEntryD<false>))
-                               : (mesh ? sizeof(CohEntryT<true>) : sizeof(CohEntryT<false>))) +
+    // (cand: coh_cands, fp32 sphere scenes only -- whose entries are CohEntryR, coh_rng0)
+    const size_t entry = f64                    ? (mesh ? sizeof(CohEntryD<true>) : sizeof(CohEntryD<false>))
+                         : cand && RT_FIFO_RNG0 ? sizeof(CohEntryR)
+                                                : (mesh ? sizeof(CohEntryT<true>) : sizeof(CohEntryT<false>));
+    return (size_t)fifo * entry +
            (sums && !f64 ? COH_SUM_BYTES : 0) + (park ? COH_PARK_BYTES : 0) + (cand ? BATCH_CAND_BYTES : 0);
 }
 constexpr size_t COH_WAVE_BYTES = coh_wave_bytes(false, true);
@@ -640,6 +663,10 @@ constexpr bool coh_cands(bool mesh, int tr, bool f64) { return !mesh && !f64 && 
 // pushing it to the FIFO for some lane to pop and regenerate (render_coherent's batch).  The
 // tree, mixed, mesh and fp64 kernels sit at their register limits and keep the FIFO for every hit.
 constexpr bool coh_adopts(bool mesh, int tr, bool f64) { return coh_cands(mesh, tr, f64); }
+// r13: in the same kernels a FIFO entry carries the path's RNG start state (CohEntryR) and the
+// camera block is read through one LDS base (camera_ray_lds ONEBASE)
+constexpr bool coh_rng0(bool mesh, int tr, bool f64) { return RT_FIFO_RNG0 && coh_cands(mesh, tr, f64); }
+constexpr bool coh_cam1(bool mesh, int tr, bool f64) { return RT_CAM_ONEBASE && coh_cands(mesh, tr, f64); }
 // LDS views by 32-bit LDS byte address (the sphere grid's flat walk and record reads)
 typedef __attribute__((address_space(3))) const uint32_t lds_cu32;
 typedef __attribute__((address_space(3))) const float4 lds_cf4;
@@ -1470,10 +1497,28 @@ __device__ __forceinline__ V3<R> sky(const V3<R>& d) {
 // kdef (render_coherent's FIFO entries): in, >= 0: the defocus disk's rejected candidates, known (the ray is
 // regenerated: the loop is skipped, its draws jumped over); -1: draw as usual and, if kout,
 // store how many candidates were rejected there
-template <class Rng>
+// ONEBASE (r13, the fp32 sphere-grid kernels): the 18 floats are read at immediate offsets from
+// one LDS byte address, which is made opaque here, where it is used, so that the compiler cannot
+// form one address per vector ahead of the loops: in those kernels it kept nine such addresses in
+// scalar registers, spilled them to VGPR lanes and read each back with a v_readlane + v_mov pair
+// in every pop pass.
+template <bool ONEBASE = false, class Rng>
 __device__ __forceinline__ Ray<float> camera_ray_lds(const float* cam, int defocus, int i, int j, Rng& rng,
                                                      int kdef = -1, int* kout = nullptr) {
-    auto v = [&](int k) { return mk(cam[3 * k], cam[3 * k + 1], cam[3 * k + 2]); };
+    [[maybe_unused]] uint32_t cam_lds = 0;
+    if constexpr (ONEBASE) {
+        cam_lds = (uint32_t)(uintptr_t)cam;   // (an LDS pointer's low word is its LDS byte address)
+        asm volatile("" : "+v"(cam_lds));
+    }
+    auto v = [&](int k) {
+        if constexpr (ONEBASE) {
+            typedef __attribute__((address_space(3))) const float lds_cf;
+            lds_cf* c = (lds_cf*)(uintptr_t)cam_lds;
+            return mk(c[3 * k], c[3 * k + 1], c[3 * k + 2]);
+        } else {
+            return mk(cam[3 * k], cam[3 * k + 1], cam[3 * k + 2]);
+        }
+    };
     const V3<float> du = v(2), dv = v(3);
     const V3<float> pixel_center = madd((float)j, dv, madd((float)i, du, v(1)));
     const float px = rng.template next_affine<float>(1.f, -0.5f);

@@ -358,11 +358,11 @@ __device__ __forceinline__ void render_lanes(const RenderParams& P, const SceneV
     if (DIAG) {
         // per-wave sums: lane 0 adds the wave's phase cycles, every lane its own counts
         const bool l0 = lane == 0;
-        const unsigned long long v[DIAG_SLOTS] = {bounce_it, bounce_act, dg.inner_it, dg.inner_act, dg.leaf_it,
-                                                  dg.leaf_act, cyc_trav, cyc_shade, l0 ? cyc_hand : 0ull,
-                                                  l0 ? __builtin_amdgcn_s_memtime() - t_start : 0ull, nseg, nflush,
-                                                  k_it1, k_it2, k_it4, 0};
-        for (int k = 0; k < DIAG_SLOTS; ++k)
+        const unsigned long long v[16] = {bounce_it, bounce_act, dg.inner_it, dg.inner_act, dg.leaf_it,
+                                          dg.leaf_act, cyc_trav, cyc_shade, l0 ? cyc_hand : 0ull,
+                                          l0 ? __builtin_amdgcn_s_memtime() - t_start : 0ull, nseg, nflush,
+                                          k_it1, k_it2, k_it4, 0};
+        for (int k = 0; k < 16; ++k)
             if (v[k]) atomicAdd(P.diag + k, v[k]);
     }
 }
@@ -433,7 +433,8 @@ __device__ __forceinline__ void flush_sample(const RenderParams& P, uint32_t pix
 // sums: fp64 sums must follow sample order).
 template <class R, bool EXACT, int BLOCK, int TRAV, bool MESH, bool DIAG = false>
 __device__ __forceinline__ void render_coherent(const RenderParams& P0, const SceneView<R>& sc, uint16_t* stack,
-                                                CohEntryX<R, MESH>* fifo, float* isum, const CohConst& kc) {
+                                                CohEntryX<R, MESH, coh_rng0(MESH, TRAV, EXACT)>* fifo, float* isum,
+                                                const CohConst& kc) {
     static_assert(!EXACT || (sizeof(R) == 8 && !DIAG), "EXACT: fp64, no instrumented build");
     // P0 is the kernel's argument (render_kernel's RenderParams, at offset 0 of the kernel-
     // argument segment).  Its fields are read through a pointer into that segment which the
@@ -473,7 +474,7 @@ __device__ __forceinline__ void render_coherent(const RenderParams& P0, const Sc
         if constexpr (EXACT)
             return camera_ray<R>(P, px, py, rr);
         else
-            return camera_ray_lds(cam, P.defocus, px, py, rr, kdef, kout);
+            return camera_ray_lds<coh_cam1(MESH, TRAV, EXACT)>(cam, P.defocus, px, py, rr, kdef, kout);
     };
     constexpr int FIFO = coh_fifo_entries(TRAV);       // primary hits the wave's FIFO holds
     const int lane = threadIdx.x & 63;
@@ -482,8 +483,11 @@ __device__ __forceinline__ void render_coherent(const RenderParams& P0, const Sc
     // item walks the grid) -- in LDS after the FIFO and the item sums, so that the bounce loop
     // carries no register for it
     constexpr bool CAND = coh_cands(MESH, TRAV, EXACT);
+    // r13: in the same kernels a FIFO entry carries the path's RNG state after start() (CohEntryR)
+    constexpr bool RNG0 = coh_rng0(MESH, TRAV, EXACT);
+    using Entry = CohEntryX<R, MESH, RNG0>;
     [[maybe_unused]] uint32_t* const clist =
-        (uint32_t*)((unsigned char*)fifo + (size_t)FIFO * sizeof(CohEntryX<R, MESH>) + (SUMS ? COH_SUM_BYTES : 0));
+        (uint32_t*)((unsigned char*)fifo + (size_t)FIFO * sizeof(Entry) + (SUMS ? COH_SUM_BYTES : 0));
     DiagCounters dg, dgb;
     unsigned long long n_bounce = 0, n_live = 0, cyc_trav = 0, cyc_shade = 0, cyc_batch = 0, n_paths = 0, n_seg = 0,
                        n_batch = 0, n_pop = 0;
@@ -550,7 +554,7 @@ __device__ __forceinline__ void render_coherent(const RenderParams& P0, const Sc
     // touched only where a hit is shaded or a path ends instead of held across the trace
     constexpr bool PARK = coh_parks(MESH, TRAV, EXACT);
     [[maybe_unused]] float* const park =
-        (float*)((unsigned char*)fifo + (size_t)FIFO * sizeof(CohEntryX<R, MESH>) + (SUMS ? COH_SUM_BYTES : 0)) + lane;
+        (float*)((unsigned char*)fifo + (size_t)FIFO * sizeof(Entry) + (SUMS ? COH_SUM_BYTES : 0)) + lane;
     auto park_thr = [&]() -> V3<R> { return mk((R)park[0], (R)park[64], (R)park[128]); };
     auto park_nsc = [&]() -> int { return __float_as_int(park[192]); };
     auto park_set = [&](V3<R> t, int n) {
@@ -579,8 +583,13 @@ __device__ __forceinline__ void render_coherent(const RenderParams& P0, const Sc
     // (the adoption sets thr and nsc in registers and no psid: not the parked state, not EXACT)
     static_assert(!ADOPT || (!PARK && !EXACT), "adopted hits: the fp32 sphere-only grid kernels");
     [[maybe_unused]] unsigned long long n_adopt = 0, n_pop_pass = 0, n_pop_lanes = 0;   // DIAG
+    // DIAG (r13): pop passes by the lanes that pop in them (1-2, 3-6, 7-16, more), those that
+    // directly follow a batch in which a lane adopted (the same pop loop) counted apart
+    [[maybe_unused]] unsigned long long n_pass_hist[8] = {};
+    [[maybe_unused]] bool after_adopt = false;   // (wave-uniform)
     auto batch = [&]([[maybe_unused]] const bool need) {
         const unsigned long long tb = DIAG ? __builtin_amdgcn_s_memtime() : 0;
+        if constexpr (DIAG && ADOPT) after_adopt = false;
         if (bi >= cur.c) {
             if (SUMS && cur.lt >= 0) {   // the item's pixel sums to HBM: lane q has pixel q
                 const float fx = isum[lane], fy = isum[64 + lane], fz = isum[128 + lane];
@@ -633,9 +642,11 @@ __device__ __forceinline__ void render_coherent(const RenderParams& P0, const Sc
         hb.t = (R)0;
         hb.id = -1;
         [[maybe_unused]] int kd = 15;
+        [[maybe_unused]] uint32_t rng0 = 0;   // RNG0: the path's RNG state after start(), for its FIFO entry
         if (px < P.W && py < P.H && P.max_depth > 0) {
             CounterRng r2;
             r2.start(hash32(P.seed32 ^ (uint32_t)(py * P.W + px)), (uint32_t)s);
+            if constexpr (RNG0) rng0 = r2.st;
             const Ray<R> pr = KDEF ? cam_ray(px, py, r2, -1, &kd) : cam_ray(px, py, r2);
             if constexpr (CAND) {
                 // (wave-uniform: the item's count, one LDS word)
@@ -658,7 +669,16 @@ __device__ __forceinline__ void render_coherent(const RenderParams& P0, const Sc
                     if (need && P.batch_adopt) {
                         adopt = true;
                         ray = pr;
-                        rng = r2;
+                        if constexpr (RNG0) {
+                            // rng0 is held across the trace for the entry, so r2.st is not: the
+                            // camera ray drew two jitters, the disc's kd rejected and one accepted
+                            // pairs (defocus) and the time; st = rng0 + draws * golden exactly
+                            // (32-bit wrap-around arithmetic on both sides)
+                            rng.st = rng0;
+                            rng.skip(3u + (P.defocus ? 2u * (uint32_t)kd + 2u : 0u));
+                        } else {
+                            rng = r2;
+                        }
                         h.t = hb.t;
                         h.td = (double)hb.t;
                         h.id = hb.id;
@@ -679,9 +699,10 @@ __device__ __forceinline__ void render_coherent(const RenderParams& P0, const Sc
         const unsigned long long hm = __ballot(push);
         if (push) {
             const uint32_t r = __builtin_amdgcn_mbcnt_hi((uint32_t)(hm >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)hm, 0u));
-            CohEntryX<R, MESH> e;
+            Entry e;
             e.t = hb.t;
             e.pix = pp;
+            if constexpr (RNG0) e.rng0 = rng0;
             if constexpr (MESH) {
                 e.sid = (uint32_t)(s - P.sample_begin);
                 if constexpr (KDEF) e.sid |= (uint32_t)min(kd, 15) << 28;
@@ -693,6 +714,7 @@ __device__ __forceinline__ void render_coherent(const RenderParams& P0, const Sc
             fifo[(head + count + r) & (FIFO - 1)] = e;
         }
         count += (uint32_t)__popcll(hm);
+        if constexpr (DIAG && ADOPT) after_adopt = __ballot(adopt) != 0;
         if (DIAG && lane == 0) {
             ++n_batch;
             cyc_batch += __builtin_amdgcn_s_memtime() - tb;
@@ -746,7 +768,7 @@ __device__ __forceinline__ void render_coherent(const RenderParams& P0, const Sc
                     const uint32_t r =
                         __builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0u));
                     if (r < count) {
-                        const CohEntryX<R, MESH> e = fifo[(head + r) & (FIFO - 1)];
+                        const Entry e = fifo[(head + r) & (FIFO - 1)];
                         pix = e.pix;
                         if constexpr (EXACT) psid = e.sid & 0xffffu;
                         const int lt = (int)(pix >> 6), q = (int)(pix & 63u), s = P.sample_begin + (int)(e.sid & 0xffffu);
@@ -756,7 +778,11 @@ __device__ __forceinline__ void render_coherent(const RenderParams& P0, const Sc
                         const int ty = LAUNDER ? (int)fma((double)t, P.tiles_x_inv, P.tiles_x_inv_half) : t / P.tiles_x;
                         const int px = (t - ty * P.tiles_x) * 8 + (q & 7), py = ty * 8 + (q >> 3);
                         elig = lt == cur.lt && s >= cur.s0 && s < cur.s0 + cur.c;
-                        rng.start(hash32(P.seed32 ^ (uint32_t)(py * P.W + px)), (uint32_t)s);
+                        // (RNG0: the batch's own state, not a re-derivation; px, py only feed the camera)
+                        if constexpr (RNG0)
+                            rng.st = e.rng0;
+                        else
+                            rng.start(hash32(P.seed32 ^ (uint32_t)(py * P.W + px)), (uint32_t)s);
                         if constexpr (KDEF) {
                             const int kd = (int)(e.sid >> 28);
                             ray = cam_ray(px, py, rng, kd == 15 ? -1 : kd);
@@ -786,6 +812,10 @@ __device__ __forceinline__ void render_coherent(const RenderParams& P0, const Sc
                 if constexpr (DIAG && ADOPT) {   // (wave-uniform) passes in which a lane popped, their lanes
                     n_pop_pass += took ? 1u : 0u;
                     n_pop_lanes += took;
+                    const int bucket = (took <= 2u ? 0 : took <= 6u ? 1 : took <= 16u ? 2 : 3) + (after_adopt ? 4 : 0);
+#pragma unroll
+                    for (int j = 0; j < 8; ++j) n_pass_hist[j] += took && j == bucket ? 1u : 0u;
+                    after_adopt = false;
                 }
                 head += took;
                 count -= took;
@@ -873,6 +903,8 @@ __device__ __forceinline__ void render_coherent(const RenderParams& P0, const Sc
             if (l0 && n_pop_pass) atomicAdd(P.diag + 27, n_pop_pass);
             if (l0 && n_pop_lanes) atomicAdd(P.diag + 28, n_pop_lanes);
             if (n_adopt) atomicAdd(P.diag + 29, n_adopt);
+            for (int j = 0; j < 8; ++j)   // 32-39: the pop passes of slot 27 by lane count
+                if (l0 && n_pass_hist[j]) atomicAdd(P.diag + 32 + j, n_pass_hist[j]);
         }
         if constexpr (MESH) {   // mesh BVH loops (batches and bounces together)
             const unsigned long long mv[4] = {dg.mnode_it + dgb.mnode_it, dg.mnode_act + dgb.mnode_act,
@@ -1069,8 +1101,8 @@ __global__ __attribute__((amdgpu_flat_work_group_size(1, BLOCK), amdgpu_waves_pe
         // (P must be this kernel's argument, its first: render_coherent re-reads it from the
         // kernel-argument segment)
         render_coherent<R, EXACT, BLOCK, TRAV, MESH, DIAG>(
-            P, sc, stack, (CohEntryX<R, MESH>*)w, (float*)(w + coh_fifo_entries(TRAV) * sizeof(CohEntryX<R, MESH>)),
-            *kc);
+            P, sc, stack, (CohEntryX<R, MESH, coh_rng0(MESH, TRAV, EXACT)>*)w,
+            (float*)(w + coh_fifo_entries(TRAV) * sizeof(CohEntryX<R, MESH, coh_rng0(MESH, TRAV, EXACT)>)), *kc);
     } else if constexpr (!EXACT) {
         // fp32: persistent lanes over the item queue (fixed-point sums, render_lanes)
         render_lanes<R, BLOCK, TRAV, MESH, DIAG>(P, sc, stack, (float*)(s_mstack + (size_t)BLOCK * P.mstack) + tid);

@@ -116,6 +116,16 @@ def main():
                 "hits_popped": d["x15"], "hits_adopted": d["hits_adopted"],
                 "adopted_share": q(d["hits_adopted"], d["hits_adopted"] + d["x15"]),
                 "batches_per_bounce_iter": q(d["k_it1"], d["bounce_it"]),
+                # pop passes by the lanes that pop in them; "after_adopt": the pass directly
+                # follows a batch in which a lane adopted, in the same shade round
+                "pop_pass_histogram": {
+                    where: dict(zip(["1-2", "3-6", "7-16", "17-64"], h))
+                    for where, h in (("other", d["pop_pass_hist"]), ("after_adopt", d["pop_pass_hist_after_adopt"]))
+                },
+                "pop_pass_share_by_lanes": {
+                    b: q(x + y, d["pop_passes"])
+                    for b, x, y in zip(["1-2", "3-6", "7-16", "17-64"], d["pop_pass_hist"], d["pop_pass_hist_after_adopt"])
+                },
             }
         if mesh:
             traced = rays + d["segments"]   # camera rays (batches) + scattered rays
