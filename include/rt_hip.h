@@ -610,6 +610,63 @@ int rt_refine_jobs(rt_ctx* ctx, rt_pixel_job* jobs, int num_jobs, const void* su
  * the call. */
 int rt_camera_rays(rt_ctx* ctx, const rt_camera* cam, const rt_pixel_job* jobs, int num_jobs, void* rays,
                    rt_path_key* keys, int32_t* ray_job, int64_t max_rays, int64_t* num_rays, void* stream);
+/* First-hit auxiliary outputs (AOVs) per job -- the guide images a denoiser asks for: albedo,
+ * normal, depth, primitive id and sky coverage -- reduced on the device without writing a ray or a
+ * hit record to memory.  jobs, valid and invalid jobs, the flat sample list, T, the scan and its
+ * single 8-byte synchronisation, the stream rules and rt_last_kernel_ms are rt_render_pixels'.
+ * Only the first segment is traced (there is no max_depth), and no RNG draw is spent beyond
+ * get_ray's.
+ * Per sample, r is the camera ray rt_camera_rays writes for it and h the rt_hit rt_trace_rays
+ * returns for r: the tree, the same traversal flags, no origin id -- the same bits.
+ * out: host struct of device pointers, each num_jobs records; a NULL member is skipped.
+ *   hits    the number of the job's samples with h.id != -1; overwritten, or added to with
+ *           accumulate = 1.  hits / sample_count is the coverage (1 - sky).
+ *   albedo  x 3, context precision: per sample the material's albedo in the context precision
+ *           (fp32: (float)rt_material.albedo) for Lambertian and metal, (1, 1, 1) -- its scatter
+ *           attenuation -- for a dielectric, 0 for a miss; summed over the job's samples.
+ *   normal  x 3, context precision: per sample h.normal, the face-oriented normal of the record
+ *           (not renormalised), 0 for a miss; summed over the job's samples.
+ *   depth, id  the nearest hit of the job: the sample with the smallest h.t, among equal t the
+ *           smallest h.id; depth = its h.t (context precision), id = its h.id (rt_hit.id's
+ *           numbering).  h.t is the ray parameter, and the camera's direction reaches the focus
+ *           plane at t = 1, so depth * focus_dist is the planar depth for a pinhole camera.  A job
+ *           with no hit gets depth = +inf, id = -1.  If only one of the two is given the other is
+ *           simply not written.
+ * Sum rule (albedo, normal): exactly rt_render_pixels', with the per-sample value in place of L.
+ * fp64 adds sequentially in sample order from 0, or from the buffer with accumulate = 1 (a miss
+ * adds 0.0); fp32 takes rintf(v 2^19), sums exactly as integers in units of 2^-28 and rounds once,
+ * with the same NaN / +-inf flags, and accumulate = 1 starts from rint((double)out 2^28) -- the
+ * exact earlier sum wherever out, a float, holds it: a sum of multiples of 2^-19 below 32 in
+ * magnitude, so {p, 0, a} then {p, a, b} equals {p, 0, a + b} bit for bit for a <= 31.
+ * Nearest hit: fp32 keeps one 64-bit word per job, (float bits of t) << 32 | (uint32_t)id, combined
+ * by unsigned minimum (t > 0.001, so bit order is numeric order); fp64 keeps (t, id) under the same
+ * comparison in the ordered reduction.  accumulate = 1 continues from what depth and id hold -- the
+ * caller's contract is that they hold an earlier call's output or (+inf, -1) -- and a missing one
+ * counts as +inf / -1.
+ * A job without samples (sample_count == 0 or pixel >= width * height) gets (0, 0, +inf, -1, 0),
+ * or is left untouched with accumulate = 1.
+ * fp64 passes: each sample is stored as a 60-byte record (7 doubles and one int32) before the
+ * ordered reduction; a pass holds floor(rt_tuning.sample_buffer_mb 2^20 / 60) samples, and a job
+ * that straddles a pass boundary continues in the next.
+ * fp32: a wave's lanes hold consecutive samples, and the lanes of one job are combined within the
+ * wave before one lane issues that job's atomics.  The environment's RT_AOV_COMBINE=0 at rt_create
+ * issues one set of atomics per sample instead; the outputs are the same bits.
+ * Errors: rt_render_pixels' (RT_ERR_NO_SCENE before an upload; RT_ERR_INVALID for a bad camera,
+ * num_jobs < 0 or a NULL jobs with num_jobs > 0; RT_ERR_LIMIT past 160 KiB of LDS or T > 2^31 - 1),
+ * and RT_ERR_INVALID for a NULL out with num_jobs > 0 or an out whose five members are all NULL.
+ * num_jobs == 0 is a no-op.  Shares rt_render_pixels' device scratch: same stream, or ordered.
+ * Not done here: walking the sphere grid or coherent per-tile batches (queries walk the tree); a
+ * sky-coloured albedo for misses (blend with the coverage yourself).
+ * Added to ABI 12 without a version bump, as rt_occluded. */
+typedef struct {
+    void*     albedo;   /* num_jobs x 3, context precision, or NULL */
+    void*     normal;   /* num_jobs x 3, context precision, or NULL */
+    void*     depth;    /* num_jobs,     context precision, or NULL */
+    int32_t*  id;       /* num_jobs, or NULL */
+    uint32_t* hits;     /* num_jobs, or NULL */
+} rt_aov_buffers;
+int rt_render_pixels_aov(rt_ctx* ctx, const rt_camera* cam, const rt_pixel_job* jobs, int num_jobs,
+                         int accumulate, const rt_aov_buffers* out, void* stream);
 /* rt_trace_rays, instrumented (fp32 sphere scenes; synchronous): counters = {node-loop wave
  * iterations, their active lanes, sphere-loop wave iterations, their active lanes}. */
 int rt_trace_rays_diag(rt_ctx* ctx, const void* rays, int num_rays, rt_hit* hits, uint64_t counters[4]);

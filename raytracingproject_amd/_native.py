@@ -93,6 +93,12 @@ class RtAdaptiveParams(C.Structure):
                 ("max_samples", C.c_uint32), ("max_step", C.c_uint32), ("pad", C.c_uint32)]
 
 
+class RtAovBuffers(C.Structure):
+    """rt_aov_buffers: rt_render_pixels_aov's device outputs, each num_jobs records or NULL."""
+    _fields_ = [("albedo", C.c_void_p), ("normal", C.c_void_p), ("depth", C.c_void_p), ("id", C.c_void_p),
+                ("hits", C.c_void_p)]
+
+
 SIGNATURES = {
     "rt_abi_version": (C.c_int, []),
     "rt_device_count": (C.c_int, []),
@@ -154,6 +160,8 @@ SIGNATURES = {
                                            C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),   # ABI 12
     "rt_refine_jobs": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.POINTER(RtAdaptiveParams),
                                  C.c_void_p, C.c_void_p]),   # ABI 12
+    "rt_render_pixels_aov": (C.c_int, [C.c_void_p, C.POINTER(RtCamera), C.c_void_p, C.c_int, C.c_int,
+                                       C.POINTER(RtAovBuffers), C.c_void_p]),   # ABI 12
 }
 
 # rt_pixel_job (16 B): rt_render_pixels' / rt_camera_rays' job -- samples [sample_begin, +sample_count) of a pixel
@@ -670,6 +678,39 @@ class Renderer:
         if segments:
             return out, d_seg.cpu().numpy()[:n].view(np.uint32)
         return out
+
+    def render_pixels_aov(self, cam: RtCamera, jobs_dev: int, n: int, albedo_dev: int | None = None,
+                          normal_dev: int | None = None, depth_dev: int | None = None, id_dev: int | None = None,
+                          hits_dev: int | None = None, accumulate: bool = False, stream: int | None = None) -> None:
+        """rt_render_pixels_aov: n jobs (RtPixelJob records, device) -> per job the first hits'
+        albedo and normal sums (n x 3 of the context precision), the nearest hit's depth (n) and
+        id (n int32) and the hit count (n uint32); a null output is skipped, accumulate continues
+        what the outputs hold.  Synchronises once on the stream, as render_pixels."""
+        out = RtAovBuffers(albedo_dev or None, normal_dev or None, depth_dev or None, id_dev or None, hits_dev or None)
+        self._check(self._L.rt_render_pixels_aov(self.ctx, C.byref(cam), C.c_void_p(jobs_dev or 0), n,
+                                                 1 if accumulate else 0, C.byref(out), C.c_void_p(stream or 0)),
+                    "rt_render_pixels_aov")
+
+    def render_pixels_aov_host(self, cam: RtCamera, jobs: np.ndarray) -> dict:
+        """rt_render_pixels_aov through device copies: jobs (RtPixelJob[n]) -> {"albedo": [n, 3],
+        "normal": [n, 3], "depth": [n] (context precision), "id": int32[n], "hits": uint32[n]}."""
+        import torch
+        jobs = self._jobs(jobs)
+        n = len(jobs)
+        tdt = torch.from_numpy(np.zeros(0, self.dtype)).dtype
+        d_jobs = torch.from_numpy((jobs if n else np.zeros(1, RtPixelJob)).view(np.uint8)).to("cuda")
+        d_alb = torch.full((max(1, n), 3), float("nan"), dtype=tdt, device="cuda")
+        d_nrm = torch.full((max(1, n), 3), float("nan"), dtype=tdt, device="cuda")
+        d_dep = torch.full((max(1, n),), float("nan"), dtype=tdt, device="cuda")
+        d_id = torch.full((max(1, n),), -2, dtype=torch.int32, device="cuda")
+        d_hits = torch.full((max(1, n),), -1, dtype=torch.int32, device="cuda")
+        stream = torch.cuda.current_stream().cuda_stream
+        torch.cuda.synchronize()
+        self.render_pixels_aov(cam, d_jobs.data_ptr(), n, d_alb.data_ptr(), d_nrm.data_ptr(), d_dep.data_ptr(),
+                               d_id.data_ptr(), d_hits.data_ptr(), False, stream)
+        torch.cuda.synchronize()
+        return {"albedo": d_alb.cpu().numpy()[:n], "normal": d_nrm.cpu().numpy()[:n], "depth": d_dep.cpu().numpy()[:n],
+                "id": d_id.cpu().numpy()[:n], "hits": d_hits.cpu().numpy()[:n].view(np.uint32)}
 
     def camera_rays(self, cam: RtCamera, jobs_dev: int, n: int, rays_dev: int, keys_dev: int,
                     ray_job_dev: int | None, max_rays: int, stream: int | None = None) -> int:

@@ -342,6 +342,27 @@ class camera:
         sums, n = sums.cpu().numpy(), n.cpu().numpy()
         return sums / n[..., None].astype(sums.dtype), n
 
+    def render_aov(self, world: hittable, samples: int | None = None) -> dict:
+        """The guide images a denoiser asks for (rt_render_pixels_aov), from the first hits of
+        samples 0 .. samples - 1 of every pixel (default: samples_per_pixel), the camera rays render
+        traces: {"albedo": [H, W, 3] and "normal": [H, W, 3], the per-job sums divided by the
+        sample count (misses count 0: blend with "coverage" for a sky colour); "depth": [H, W], the
+        nearest hit's ray parameter (times focus_dist: planar depth; +inf for sky); "id": int32[H, W],
+        its primitive in the upload's order (-1 for sky); "coverage": [H, W], hits / samples}."""
+        self.initialize()
+        if self._renderer is None:
+            self._renderer = N.Renderer(self.device, self.seed, self.precision)
+        self._upload(self._renderer, world)
+        n = self.samples_per_pixel if samples is None else samples
+        W, H = self._cam.image_width, self._cam.image_height
+        jobs = np.zeros(W * H, N.RtPixelJob)
+        jobs["pixel"], jobs["sample_count"] = np.arange(W * H), n
+        o = self._renderer.render_pixels_aov_host(self._cam, jobs)
+        dt = o["albedo"].dtype.type
+        return {"albedo": (o["albedo"] / dt(n)).reshape(H, W, 3), "normal": (o["normal"] / dt(n)).reshape(H, W, 3),
+                "depth": o["depth"].reshape(H, W), "id": o["id"].reshape(H, W),
+                "coverage": (o["hits"].astype(o["albedo"].dtype) / dt(n)).reshape(H, W)}
+
 
 def write_ppm(out, rgb: np.ndarray) -> None:
     """PPM P3 exactly as camera.h:35 and color.h:32-34 print it."""

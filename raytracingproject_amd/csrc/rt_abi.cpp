@@ -225,6 +225,14 @@ rt_ctx* rt_create(int device, uint64_t seed, int precision) {
         delete c;
         return nullptr;
     }
+    // RT_AOV_COMBINE: "1" (rt_render_pixels_aov reduces a wave's lanes of one job before the
+    // atomics; the default, also unset or empty) or "0" (one set of atomics per sample).  The
+    // outputs do not depend on it.
+    if (!parse_batch_adopt(getenv("RT_AOV_COMBINE"), c->aov_combine)) {
+        fprintf(stderr, "rt_create: RT_AOV_COMBINE must be 0 or 1\n");
+        delete c;
+        return nullptr;
+    }
     c->device = device;
     c->seed = seed;
     c->precision = precision;
@@ -264,6 +272,7 @@ void rt_destroy(rt_ctx* c) {
     (void)hipFree(c->d_px_sseg);
     (void)hipFree(c->d_px_sq);
     (void)hipFree(c->d_px_sqflags);
+    (void)hipFree(c->d_aov_near);
     (void)hipFree(c->d_gather);
     for (auto& a : c->accum) {
         (void)hipFree(a.acc);
@@ -1261,6 +1270,80 @@ int rt_render_pixels_moments(rt_ctx* c, const rt_camera* cam, const rt_pixel_job
                              int accumulate, void* out_sums, void* out_sumsq, uint32_t* out_segments, void* stream) {
     return render_pixels(c, "rt_render_pixels_moments", cam, jobs, num_jobs, max_depth, accumulate, out_sums, true,
                          out_sumsq, out_segments, stream);
+}
+
+// rt_render_pixels_aov: rt_render_pixels' checks, scan and scratch; one first-hit kernel in place
+// of the path kernel, the sums' seed and finalize launches once per summed output.
+int rt_render_pixels_aov(rt_ctx* c, const rt_camera* cam, const rt_pixel_job* jobs, int num_jobs, int accumulate,
+                         const rt_aov_buffers* out, void* stream) {
+    const char* what = "rt_render_pixels_aov";
+    if (!c) return RT_ERR_INVALID;
+    if (!c->has_scene) return fail(c, RT_ERR_NO_SCENE, "%s before rt_upload_scene", what);
+    int rc = check_camera(c, cam);
+    if (rc) return rc;
+    if (num_jobs < 0 || (num_jobs > 0 && (!jobs || !out)))
+        return fail(c, RT_ERR_INVALID, "%s: %d jobs, jobs %p, out %p", what, num_jobs, (const void*)jobs,
+                    (const void*)out);
+    if (out && !out->albedo && !out->normal && !out->depth && !out->id && !out->hits)
+        return fail(c, RT_ERR_INVALID, "%s: every member of rt_aov_buffers is NULL", what);
+    const bool f64 = c->precision == RT_PREC_F64;
+    RenderParams P;
+    size_t lds;
+    if ((rc = query_setup(c, what, P, lds, cam))) return rc;
+    if (num_jobs == 0) return RT_OK;
+    const rt_aov_buffers o = *out;
+    const size_t nj = (size_t)num_jobs;
+    const int acc = accumulate ? 1 : 0;
+    hipStream_t st = stream ? (hipStream_t)stream : c->stream;
+    HIPCHK(c, hipEventRecord(c->ev0, st));
+    unsigned long long total = 0;
+    if ((rc = pixel_scan(c, cam, jobs, num_jobs, st, total))) return rc;
+    if (total > 0x7fffffffull) return fail(c, RT_ERR_LIMIT, "%s: %llu samples (> 2^31 - 1)", what, total);
+    const unsigned long long* off = c->d_px_offsets;
+    if ((rc = grow(c, &c->d_aov_near, &c->aov_near_cap, nj * 16))) return rc;
+    hipError_t e = hipSuccess;
+    if (!f64) {
+        // albedo's sums and flags, then normal's, in rt_render_pixels' scratch
+        if ((rc = grow(c, (void**)&c->d_px_acc, &c->px_acc_cap, nj * 6 * sizeof(long long)))) return rc;
+        if ((rc = grow(c, (void**)&c->d_px_flags, &c->px_flags_cap, nj * 2 * sizeof(uint32_t)))) return rc;
+        long long* acc_a = o.albedo ? c->d_px_acc : nullptr;
+        long long* acc_n = o.normal ? c->d_px_acc + nj * 3 : nullptr;
+        uint32_t *fl_a = c->d_px_flags, *fl_n = c->d_px_flags + nj;
+        unsigned long long* near = (o.depth || o.id) ? (unsigned long long*)c->d_aov_near : nullptr;
+        if (acc_a) e = launch_pixels_seed(off, num_jobs, acc, (const float*)o.albedo, acc_a, fl_a, nullptr, st);
+        if (e == hipSuccess && acc_n)
+            e = launch_pixels_seed(off, num_jobs, acc, (const float*)o.normal, acc_n, fl_n, nullptr, st);
+        if (e == hipSuccess && (near || o.hits))
+            e = launch_aov_seed(off, num_jobs, acc, (const float*)o.depth, o.id, near, o.hits, st);
+        if (e == hipSuccess)
+            e = launch_aov_f32(P, lds, st, jobs, off, num_jobs, total, c->d_remap, (unsigned long long*)acc_a, fl_a,
+                               (unsigned long long*)acc_n, fl_n, near, o.hits, c->n_cu, c->aov_combine != 0);
+        if (e == hipSuccess && acc_a) e = launch_pixels_finalize(off, num_jobs, acc, acc_a, fl_a, (float*)o.albedo, st);
+        if (e == hipSuccess && acc_n) e = launch_pixels_finalize(off, num_jobs, acc, acc_n, fl_n, (float*)o.normal, st);
+        if (e == hipSuccess && near) e = launch_aov_finalize(off, num_jobs, acc, near, (float*)o.depth, o.id, st);
+    } else {
+        // passes of at most floor(sample_buffer_mb 2^20 / 60) samples, reduced in order; the first
+        // one also fills the jobs without samples, so it runs even when T = 0
+        const unsigned long long fit = ((unsigned long long)c->tuning.sample_buffer_mb << 20) / AOV_SAMPLE_BYTES;
+        const unsigned long long pass = std::max(1ull, std::min(fit, total));
+        if ((rc = grow(c, (void**)&c->d_px_samples, &c->px_samples_cap, (size_t)pass * 7 * sizeof(double)))) return rc;
+        if ((rc = grow(c, (void**)&c->d_px_sseg, &c->px_sseg_cap, (size_t)pass * sizeof(int32_t)))) return rc;
+        unsigned long long q0 = 0;
+        do {
+            const unsigned long long q1 = std::min(total, q0 + pass);
+            e = launch_aov_f64(P, lds, st, jobs, off, num_jobs, total, q0, (int)(q1 - q0), c->d_remap, c->d_px_samples,
+                               (int32_t*)c->d_px_sseg, c->n_cu);
+            if (e == hipSuccess)
+                e = launch_aov_reduce(off, num_jobs, q0, q1, c->d_px_samples, (const int32_t*)c->d_px_sseg, acc,
+                                      c->d_aov_near, (double*)o.albedo, (double*)o.normal, (double*)o.depth, o.id,
+                                      o.hits, st);
+            q0 = q1;
+        } while (q0 < total && e == hipSuccess);
+    }
+    if (e != hipSuccess) return fail(c, RT_ERR_HIP, "aov launch: %s", hipGetErrorString(e));
+    HIPCHK(c, hipEventRecord(c->ev1, st));
+    c->timed = true;
+    return RT_OK;
 }
 
 int rt_refine_jobs(rt_ctx* c, rt_pixel_job* jobs, int num_jobs, const void* sums, const void* sumsq,

@@ -107,6 +107,13 @@ struct rt_ctx {
     size_t px_sq_cap = 0;
     uint32_t* d_px_sqflags = nullptr;
     size_t px_sqflags_cap = 0;
+    // rt_render_pixels_aov: the per-job nearest hit (num_jobs x 16 B: fp32 one packed word, fp64
+    // the (t, id) carried between passes); its sums use d_px_acc / d_px_flags twice over, its
+    // fp64 records d_px_samples / d_px_sseg.  aov_combine: the wave combine before the atomics,
+    // from the environment's RT_AOV_COMBINE at rt_create
+    void* d_aov_near = nullptr;
+    size_t aov_near_cap = 0;
+    int aov_combine = 1;
     void* d_gather = nullptr;  // rt_render_frame_multi: all contexts' shards
     size_t gather_cap = 0;
 

@@ -121,6 +121,37 @@ hipError_t launch_pixels_seed_moments(const unsigned long long* offsets, int num
 hipError_t launch_pixels_finalize_moments(const unsigned long long* offsets, int num_jobs, int accumulate,
                                           const unsigned long long* sq, const uint32_t* sqflags, float* out_sumsq,
                                           hipStream_t stream);
+// bytes of one fp64 first-hit record (7 doubles: albedo, normal, t; one int32 id, kept in two
+// arrays): a pass of rt_render_pixels_aov holds floor(sample_buffer_mb 2^20 / AOV_SAMPLE_BYTES)
+constexpr size_t AOV_SAMPLE_BYTES = 60;
+// rt_render_pixels_aov (csrc/rt_aov.h): first-hit albedo, normal, depth, id and hit count per job
+// over flat samples [q_begin, q_begin + n) of the list's `total`; remap: rt_trace_rays' id map.
+// Not persistent (one segment per sample); the grid is what stays resident, as launch_pixels_*.
+// fp32 adds into acc_albedo / acc_normal (num_jobs x 3 sums in units of 2^-28, with their flags;
+// launch_pixels_seed / launch_pixels_finalize before and after), nearest (num_jobs words,
+// float bits of t << 32 | id; launch_aov_seed / launch_aov_finalize) and hits; any of the four
+// may be null.  combine: a wave's lanes of one job are reduced before the atomics (the default)
+// or every sample issues its own; the outputs do not depend on it.
+hipError_t launch_aov_f32(const RenderParams& P, size_t lds_bytes, hipStream_t stream, const void* jobs,
+                          const unsigned long long* offsets, int num_jobs, unsigned long long total, const int* remap,
+                          unsigned long long* acc_albedo, uint32_t* flags_albedo, unsigned long long* acc_normal,
+                          uint32_t* flags_normal, unsigned long long* nearest, uint32_t* hits, int n_cu, bool combine);
+hipError_t launch_aov_seed(const unsigned long long* offsets, int num_jobs, int accumulate, const float* depth,
+                           const int32_t* id, unsigned long long* nearest, uint32_t* hits, hipStream_t stream);
+hipError_t launch_aov_finalize(const unsigned long long* offsets, int num_jobs, int accumulate,
+                               const unsigned long long* nearest, float* depth, int32_t* id, hipStream_t stream);
+// fp64 stores sample q's record at q - q_begin of records (n x 7 doubles) and record_ids (n);
+// launch_aov_reduce adds one pass's records [q_begin, q_end) per job in sample order into the
+// outputs (each may be null) and keeps the nearest (t, id), carried between passes in `carry`
+// (num_jobs x 16 bytes)
+hipError_t launch_aov_f64(const RenderParams& P, size_t lds_bytes, hipStream_t stream, const void* jobs,
+                          const unsigned long long* offsets, int num_jobs, unsigned long long total,
+                          unsigned long long q_begin, int n, const int* remap, double* records, int32_t* record_ids,
+                          int n_cu);
+hipError_t launch_aov_reduce(const unsigned long long* offsets, int num_jobs, unsigned long long q_begin,
+                             unsigned long long q_end, const double* records, const int32_t* record_ids,
+                             int accumulate, void* carry, double* albedo, double* normal, double* depth, int32_t* id,
+                             uint32_t* hits, hipStream_t stream);
 // rt_refine_jobs: jobs (rt_pixel_job, device) rewritten in place from sums / sumsq (num_jobs x 3
 // of elem_bytes 4 or 8) by rt_adaptive_params' fields; stats: two words, added to
 hipError_t launch_refine_jobs(void* jobs, int num_jobs, const void* sums, const void* sumsq, int elem_bytes,

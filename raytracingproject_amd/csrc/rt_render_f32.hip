@@ -8,6 +8,7 @@
 #include "rt_radiance.h"
 #include "rt_pixels.h"
 #include "rt_moments.h"
+#include "rt_aov.h"
 
 namespace rtx {
 
@@ -212,6 +213,51 @@ hipError_t launch_pixels_moments_f32(const RenderParams& P, size_t lds_bytes, hi
         hipLaunchKernelGGL(kern, dim3(cap(radiance_grid<B>(v, lds_bytes, n, n_cu))), dim3(B), lds_bytes, stream, P, j,
                            offsets, num_jobs, total, q_begin, n, acc, flags, segments, sq, sqflags);
     }
+    return hipGetLastError();
+}
+
+// First-hit auxiliary outputs (rt_render_pixels_aov), fp32: launch_trace_f32's traversal flags,
+// so a sample's record is rt_trace_rays'; launch_pixels_f32's register budgets and grid bound.
+template <bool MESH, bool COMBINE>
+static hipError_t launch_aov(const RenderParams& P, size_t lds_bytes, hipStream_t stream, const PixelJob* jobs,
+                             const unsigned long long* offsets, int num_jobs, unsigned long long total,
+                             const int* remap, const AovAcc& A, int n_cu) {
+    constexpr int B = TRACE_BLOCK;
+    constexpr int TS = TRAV_SELROOT | TRAV_B128 | TRAV_CULL, TM = TRAV_SELROOT | TRAV_CULL | TRAV_MIFIF;
+    auto* kern = aov_kernel<float, false, B, MESH ? RADIANCE_MESH_WPE : RADIANCE_WPE, MESH ? TM : TS, MESH, COMBINE>;
+    static const int v = radiance_vgprs((const void*)kern);
+    hipLaunchKernelGGL(kern, dim3(radiance_grid<B>(v, lds_bytes, (int)total, n_cu)), dim3(B), lds_bytes, stream, P,
+                       jobs, offsets, num_jobs, total, 0ull, (int)total, remap, A, (float*)nullptr, (int32_t*)nullptr);
+    return hipGetLastError();
+}
+
+hipError_t launch_aov_f32(const RenderParams& P, size_t lds_bytes, hipStream_t stream, const void* jobs,
+                          const unsigned long long* offsets, int num_jobs, unsigned long long total, const int* remap,
+                          unsigned long long* acc_albedo, uint32_t* flags_albedo, unsigned long long* acc_normal,
+                          uint32_t* flags_normal, unsigned long long* nearest, uint32_t* hits, int n_cu, bool combine) {
+    if (total == 0) return hipSuccess;
+    const PixelJob* j = (const PixelJob*)jobs;
+    const AovAcc A{acc_albedo, flags_albedo, acc_normal, flags_normal, nearest, hits};
+    if (P.n_mnodes > 0)
+        return combine ? launch_aov<true, true>(P, lds_bytes, stream, j, offsets, num_jobs, total, remap, A, n_cu)
+                       : launch_aov<true, false>(P, lds_bytes, stream, j, offsets, num_jobs, total, remap, A, n_cu);
+    return combine ? launch_aov<false, true>(P, lds_bytes, stream, j, offsets, num_jobs, total, remap, A, n_cu)
+                   : launch_aov<false, false>(P, lds_bytes, stream, j, offsets, num_jobs, total, remap, A, n_cu);
+}
+
+hipError_t launch_aov_seed(const unsigned long long* offsets, int num_jobs, int accumulate, const float* depth,
+                           const int32_t* id, unsigned long long* nearest, uint32_t* hits, hipStream_t stream) {
+    if (num_jobs <= 0) return hipSuccess;
+    hipLaunchKernelGGL(aov_seed_kernel<float>, dim3((unsigned)((num_jobs + 255) / 256)), dim3(256), 0, stream, offsets,
+                       num_jobs, accumulate, depth, id, nearest, hits);
+    return hipGetLastError();
+}
+
+hipError_t launch_aov_finalize(const unsigned long long* offsets, int num_jobs, int accumulate,
+                               const unsigned long long* nearest, float* depth, int32_t* id, hipStream_t stream) {
+    if (num_jobs <= 0) return hipSuccess;
+    hipLaunchKernelGGL(aov_finalize_kernel<float>, dim3((unsigned)((num_jobs + 255) / 256)), dim3(256), 0, stream,
+                       offsets, num_jobs, accumulate, nearest, depth, id);
     return hipGetLastError();
 }
 

@@ -5,6 +5,7 @@
 #include "rt_radiance.h"
 #include "rt_pixels.h"
 #include "rt_moments.h"
+#include "rt_aov.h"
 
 #include <hipcub/hipcub.hpp>
 
@@ -410,6 +411,41 @@ hipError_t launch_pixels_finalize(const unsigned long long* offsets, int num_job
     if (num_jobs <= 0) return hipSuccess;
     hipLaunchKernelGGL(px_finalize_kernel, dim3((unsigned)((num_jobs + 255) / 256)), dim3(256), 0, stream, offsets,
                        num_jobs, accumulate, acc, flags, out_sums);
+    return hipGetLastError();
+}
+
+// First-hit auxiliary outputs (rt_render_pixels_aov), fp64: launch_trace_f64's box tests, so a
+// sample's record is rt_trace_rays'; launch_pixels_f64's register budget and grid bound.
+hipError_t launch_aov_f64(const RenderParams& P, size_t lds_bytes, hipStream_t stream, const void* jobs,
+                          const unsigned long long* offsets, int num_jobs, unsigned long long total,
+                          unsigned long long q_begin, int n, const int* remap, double* records, int32_t* record_ids,
+                          int n_cu) {
+    if (n <= 0) return hipSuccess;
+    constexpr int B = TRACE_BLOCK;
+    const PixelJob* j = (const PixelJob*)jobs;
+    const AovAcc none{};
+    if (P.n_mnodes > 0) {
+        auto* kern = aov_kernel<double, true, B, 4, TRAV_F32BOX, true, false>;
+        static const int v = radiance_vgprs((const void*)kern);
+        hipLaunchKernelGGL(kern, dim3(radiance_grid<B>(v, lds_bytes, n, n_cu)), dim3(B), lds_bytes, stream, P, j,
+                           offsets, num_jobs, total, q_begin, n, remap, none, records, record_ids);
+    } else {
+        auto* kern = aov_kernel<double, true, B, 4, TRAV_F32BOX, false, false>;
+        static const int v = radiance_vgprs((const void*)kern);
+        hipLaunchKernelGGL(kern, dim3(radiance_grid<B>(v, lds_bytes, n, n_cu)), dim3(B), lds_bytes, stream, P, j,
+                           offsets, num_jobs, total, q_begin, n, remap, none, records, record_ids);
+    }
+    return hipGetLastError();
+}
+
+hipError_t launch_aov_reduce(const unsigned long long* offsets, int num_jobs, unsigned long long q_begin,
+                             unsigned long long q_end, const double* records, const int32_t* record_ids,
+                             int accumulate, void* carry, double* albedo, double* normal, double* depth, int32_t* id,
+                             uint32_t* hits, hipStream_t stream) {
+    if (num_jobs <= 0) return hipSuccess;
+    hipLaunchKernelGGL(aov_reduce_kernel<double>, dim3((unsigned)((num_jobs + 255) / 256)), dim3(256), 0, stream,
+                       offsets, num_jobs, q_begin, q_end, records, record_ids, accumulate, (AovNear*)carry, albedo,
+                       normal, depth, id, hits);
     return hipGetLastError();
 }
 
