@@ -15,6 +15,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <functional>
 #include <string>
 #include <vector>
 
@@ -1119,8 +1120,9 @@ int rt_radiance_rays(rt_ctx* c, const void* rays, int n, const rt_path_key* keys
 
 // rt_render_pixels / rt_camera_rays: offsets = the exclusive scan of the valid jobs' counts on
 // `st` (c->d_px_offsets), and T = offsets[num_jobs] read back -- the calls' one synchronisation.
-static int pixel_scan(rt_ctx* c, const rt_camera* cam, const rt_pixel_job* jobs, int num_jobs, hipStream_t st,
-                      unsigned long long& total) {
+// T > 2^31 - 1 is RT_ERR_LIMIT, the only one from here, and `total` holds T all the same.
+static int pixel_scan(rt_ctx* c, const char* what, const rt_camera* cam, const rt_pixel_job* jobs, int num_jobs,
+                      hipStream_t st, unsigned long long& total) {
     int rc;
     if ((rc = grow(c, (void**)&c->d_px_offsets, &c->px_offsets_cap, ((size_t)num_jobs + 1) * sizeof(unsigned long long))))
         return rc;
@@ -1131,6 +1133,7 @@ static int pixel_scan(rt_ctx* c, const rt_camera* cam, const rt_pixel_job* jobs,
     HIPCHK(c, launch_pixel_scan(jobs, num_jobs, npix, c->d_px_offsets, c->d_px_scan, &tmp, st));
     HIPCHK(c, hipMemcpyAsync(&total, c->d_px_offsets + num_jobs, sizeof(total), hipMemcpyDeviceToHost, st));
     HIPCHK(c, hipStreamSynchronize(st));
+    if (total > 0x7fffffffull) return fail(c, RT_ERR_LIMIT, "%s: %llu samples (> 2^31 - 1)", what, total);
     return RT_OK;
 }
 
@@ -1150,9 +1153,9 @@ int rt_camera_rays(rt_ctx* c, const rt_camera* cam, const rt_pixel_job* jobs, in
     hipStream_t st = stream ? (hipStream_t)stream : c->stream;
     HIPCHK(c, hipEventRecord(c->ev0, st));
     unsigned long long total = 0;
-    if ((rc = pixel_scan(c, cam, jobs, num_jobs, st, total))) return rc;
-    if (num_rays) *num_rays = (int64_t)total;
-    if (total > 0x7fffffffull) return fail(c, RT_ERR_LIMIT, "rt_camera_rays: %llu samples (> 2^31 - 1)", total);
+    rc = pixel_scan(c, "rt_camera_rays", cam, jobs, num_jobs, st, total);
+    if (num_rays && (rc == RT_OK || rc == RT_ERR_LIMIT)) *num_rays = (int64_t)total;   // (the scan has run)
+    if (rc) return rc;
     if ((int64_t)total > max_rays)
         return fail(c, RT_ERR_INVALID, "rt_camera_rays: %llu rays for buffers of %lld", total, (long long)max_rays);
     RenderParams P;
@@ -1168,31 +1171,77 @@ int rt_camera_rays(rt_ctx* c, const rt_camera* cam, const rt_pixel_job* jobs, in
     return RT_OK;
 }
 
-// rt_render_pixels, and with `moments` rt_render_pixels_moments: the same launches, the second
-// moment's siblings (csrc/rt_moments.h) in place of the path kernel (fp32) or the reduction (fp64).
-static int render_pixels(rt_ctx* c, const char* what, const rt_camera* cam, const rt_pixel_job* jobs, int num_jobs,
-                         int max_depth, int accumulate, void* out_sums, bool moments, void* out_sumsq,
-                         uint32_t* out_segments, void* stream) {
+// What a job-list query (rt_render_pixels, rt_render_pixels_moments, rt_render_pixels_aov) holds
+// once job_query_begin has run.
+struct JobQuery {
+    RenderParams P;
+    size_t lds;
+    hipStream_t st;
+    unsigned long long total;   // T = offsets[num_jobs] (c->d_px_offsets), where the list was scanned
+};
+
+// The prologue of those calls, in the order their errors are found: the context, the scene, the
+// camera; the call's own argument checks (`args`: RT_OK, or what fail returned); query_setup; then,
+// for a list that has jobs, the stream, ev0 and -- with `scan` -- pixel_scan.  A caller returns
+// what this returns where that is an error or num_jobs == 0.
+static int job_query_begin(rt_ctx* c, const char* what, const rt_camera* cam, const rt_pixel_job* jobs, int num_jobs,
+                           void* stream, bool scan, const std::function<int()>& args, JobQuery& q) {
     if (!c) return RT_ERR_INVALID;
     if (!c->has_scene) return fail(c, RT_ERR_NO_SCENE, "%s before rt_upload_scene", what);
     int rc = check_camera(c, cam);
     if (rc) return rc;
-    if (num_jobs < 0 || (num_jobs > 0 && (!jobs || !out_sums || (moments && !out_sumsq))))
-        return fail(c, RT_ERR_INVALID, "%s: %d jobs, jobs %p, out_sums %p, out_sumsq %p", what, num_jobs,
-                    (const void*)jobs, out_sums, out_sumsq);
-    const bool f64 = c->precision == RT_PREC_F64;
-    if (f64 && max_depth > 64)
-        return fail(c, RT_ERR_LIMIT, "fp64 path keeps at most 64 bounces (max_depth %d)", max_depth);
-    RenderParams P;
-    size_t lds;
-    if ((rc = query_setup(c, what, P, lds, cam))) return rc;
+    if ((rc = args())) return rc;
+    if ((rc = query_setup(c, what, q.P, q.lds, cam))) return rc;
+    q.total = 0;
     if (num_jobs == 0) return RT_OK;
-    P.max_depth = max_depth;
-    const size_t nj = (size_t)num_jobs;
-    if (!c->d_queue_px) HIPCHK(c, hipMalloc((void**)&c->d_queue_px, QUEUE_CTRL_BYTES));
-    P.queue = c->d_queue_px;
-    hipStream_t st = stream ? (hipStream_t)stream : c->stream;
-    HIPCHK(c, hipEventRecord(c->ev0, st));
+    q.st = stream ? (hipStream_t)stream : c->stream;
+    HIPCHK(c, hipEventRecord(c->ev0, q.st));
+    return scan ? pixel_scan(c, what, cam, jobs, num_jobs, q.st, q.total) : RT_OK;
+}
+
+// The fp64 passes of those calls: a sample's record is doubles and one 32-bit word, sample_bytes
+// in all, kept in two arrays (c->d_px_samples, c->d_px_sseg) that hold a pass -- at most
+// floor(sample_buffer_mb 2^20 / sample_bytes) samples.  run(q0, q1) launches and reduces flat
+// samples [q0, q1), in order; the first pass also fills the jobs without samples, so it runs even
+// when T = 0.  e: the first launch error.
+static int sample_passes(rt_ctx* c, unsigned long long total, size_t sample_bytes, hipError_t& e,
+                         const std::function<hipError_t(unsigned long long, unsigned long long)>& run) {
+    const unsigned long long fit = ((unsigned long long)c->tuning.sample_buffer_mb << 20) / sample_bytes;
+    const unsigned long long pass = std::max(1ull, std::min(fit, total));
+    int rc;
+    if ((rc = grow(c, (void**)&c->d_px_samples, &c->px_samples_cap, (size_t)pass * (sample_bytes - sizeof(uint32_t)))))
+        return rc;
+    if ((rc = grow(c, (void**)&c->d_px_sseg, &c->px_sseg_cap, (size_t)pass * sizeof(uint32_t)))) return rc;
+    unsigned long long q0 = 0;
+    do {
+        const unsigned long long q1 = std::min(total, q0 + pass);
+        e = run(q0, q1);
+        q0 = q1;
+    } while (q0 < total && e == hipSuccess);
+    return RT_OK;
+}
+
+// rt_render_pixels, and with `moments` rt_render_pixels_moments: the same launches, with the
+// second moment's path kernel (fp32, csrc/rt_moments.h) or reduction (fp64).
+static int render_pixels(rt_ctx* c, const char* what, const rt_camera* cam, const rt_pixel_job* jobs, int num_jobs,
+                         int max_depth, int accumulate, void* out_sums, bool moments, void* out_sumsq,
+                         uint32_t* out_segments, void* stream) {
+    JobQuery q;
+    // (max_depth <= 0 renders nothing and needs no scan)
+    int rc = job_query_begin(c, what, cam, jobs, num_jobs, stream, max_depth > 0, [&] {
+        if (num_jobs < 0 || (num_jobs > 0 && (!jobs || !out_sums || (moments && !out_sumsq))))
+            return fail(c, RT_ERR_INVALID, "%s: %d jobs, jobs %p, out_sums %p, out_sumsq %p", what, num_jobs,
+                        (const void*)jobs, out_sums, out_sumsq);
+        if (c->precision == RT_PREC_F64 && max_depth > 64)
+            return fail(c, RT_ERR_LIMIT, "fp64 path keeps at most 64 bounces (max_depth %d)", max_depth);
+        return (int)RT_OK;
+    }, q);
+    if (rc || num_jobs == 0) return rc;
+    RenderParams& P = q.P;
+    const size_t lds = q.lds, nj = (size_t)num_jobs;
+    const unsigned long long total = q.total;
+    const hipStream_t st = q.st;
+    const int acc = accumulate ? 1 : 0;
     hipError_t e = hipSuccess;
     if (max_depth <= 0) {   // camera_cpu.h:9-10: no path, no light; accumulate: nothing to add
         if (!accumulate) {
@@ -1201,22 +1250,22 @@ static int render_pixels(rt_ctx* c, const char* what, const rt_camera* cam, cons
             if (e == hipSuccess && out_segments) e = hipMemsetAsync(out_segments, 0, nj * sizeof(uint32_t), st);
         }
     } else {
-        unsigned long long total = 0;
-        if ((rc = pixel_scan(c, cam, jobs, num_jobs, st, total))) return rc;
-        if (total > 0x7fffffffull) return fail(c, RT_ERR_LIMIT, "%s: %llu samples (> 2^31 - 1)", what, total);
+        P.max_depth = max_depth;
+        if (!c->d_queue_px) HIPCHK(c, hipMalloc((void**)&c->d_queue_px, QUEUE_CTRL_BYTES));
+        P.queue = c->d_queue_px;
         const unsigned long long* off = c->d_px_offsets;
-        if (!f64) {
+        if (c->precision != RT_PREC_F64) {
             if ((rc = grow(c, (void**)&c->d_px_acc, &c->px_acc_cap, nj * 3 * sizeof(long long)))) return rc;
             if ((rc = grow(c, (void**)&c->d_px_flags, &c->px_flags_cap, nj * sizeof(uint32_t)))) return rc;
             if (moments) {
                 if ((rc = grow(c, (void**)&c->d_px_sq, &c->px_sq_cap, nj * 6 * sizeof(unsigned long long)))) return rc;
                 if ((rc = grow(c, (void**)&c->d_px_sqflags, &c->px_sqflags_cap, nj * sizeof(uint32_t)))) return rc;
             }
-            e = launch_pixels_seed(off, num_jobs, accumulate ? 1 : 0, (const float*)out_sums, c->d_px_acc, c->d_px_flags,
-                                   out_segments, st);
+            e = launch_pixels_seed(off, num_jobs, acc, (const float*)out_sums, c->d_px_acc, c->d_px_flags, out_segments,
+                                   st);
             if (e == hipSuccess && moments)
-                e = launch_pixels_seed_moments(off, num_jobs, accumulate ? 1 : 0, (const float*)out_sumsq, c->d_px_sq,
-                                               c->d_px_sqflags, st);
+                e = launch_pixels_seed_moments(off, num_jobs, acc, (const float*)out_sumsq, c->d_px_sq, c->d_px_sqflags,
+                                               st);
             if (e == hipSuccess) e = hipMemsetAsync(c->d_queue_px, 0, QUEUE_CTRL_BYTES, st);
             if (e == hipSuccess)
                 e = moments ? launch_pixels_moments_f32(P, lds, st, jobs, off, num_jobs, total, 0, (int)total,
@@ -1225,33 +1274,24 @@ static int render_pixels(rt_ctx* c, const char* what, const rt_camera* cam, cons
                             : launch_pixels_f32(P, lds, st, jobs, off, num_jobs, total, 0, (int)total,
                                                 (unsigned long long*)c->d_px_acc, c->d_px_flags, out_segments, c->n_cu);
             if (e == hipSuccess)
-                e = launch_pixels_finalize(off, num_jobs, accumulate ? 1 : 0, c->d_px_acc, c->d_px_flags,
-                                           (float*)out_sums, st);
+                e = launch_pixels_finalize(off, num_jobs, acc, c->d_px_acc, c->d_px_flags, (float*)out_sums, st);
             if (e == hipSuccess && moments)
-                e = launch_pixels_finalize_moments(off, num_jobs, accumulate ? 1 : 0, c->d_px_sq, c->d_px_sqflags,
-                                                   (float*)out_sumsq, st);
+                e = launch_pixels_finalize_moments(off, num_jobs, acc, c->d_px_sq, c->d_px_sqflags, (float*)out_sumsq,
+                                                   st);
         } else {
-            // passes of at most floor(sample_buffer_mb 2^20 / 28) samples, reduced in order; the
-            // first one also zeroes the jobs without samples, so it runs even when T = 0
-            const unsigned long long fit = ((unsigned long long)c->tuning.sample_buffer_mb << 20) / PX_SAMPLE_BYTES;
-            const unsigned long long pass = std::max(1ull, std::min(fit, total));
-            if ((rc = grow(c, (void**)&c->d_px_samples, &c->px_samples_cap, (size_t)pass * 3 * sizeof(double)))) return rc;
-            if ((rc = grow(c, (void**)&c->d_px_sseg, &c->px_sseg_cap, (size_t)pass * sizeof(uint32_t)))) return rc;
-            unsigned long long q0 = 0;
-            do {
-                const unsigned long long q1 = std::min(total, q0 + pass);
-                e = hipMemsetAsync(c->d_queue_px, 0, QUEUE_CTRL_BYTES, st);
-                if (e == hipSuccess)
-                    e = launch_pixels_f64(P, lds, st, jobs, off, num_jobs, total, q0, (int)(q1 - q0), c->d_px_samples,
+            rc = sample_passes(c, total, PX_SAMPLE_BYTES, e, [&](unsigned long long q0, unsigned long long q1) {
+                hipError_t pe = hipMemsetAsync(c->d_queue_px, 0, QUEUE_CTRL_BYTES, st);
+                if (pe == hipSuccess)
+                    pe = launch_pixels_f64(P, lds, st, jobs, off, num_jobs, total, q0, (int)(q1 - q0), c->d_px_samples,
                                           c->d_px_sseg, c->n_cu, moments ? c->tuning.grid_workgroups : 0);
-                if (e == hipSuccess)
-                    e = moments ? launch_pixels_reduce_moments(off, num_jobs, q0, q1, c->d_px_samples, c->d_px_sseg,
-                                                               accumulate ? 1 : 0, (double*)out_sums,
-                                                               (double*)out_sumsq, out_segments, st)
-                                : launch_pixels_reduce(off, num_jobs, q0, q1, c->d_px_samples, c->d_px_sseg,
-                                                       accumulate ? 1 : 0, (double*)out_sums, out_segments, st);
-                q0 = q1;
-            } while (q0 < total && e == hipSuccess);
+                if (pe == hipSuccess)
+                    pe = moments ? launch_pixels_reduce_moments(off, num_jobs, q0, q1, c->d_px_samples, c->d_px_sseg, acc,
+                                                                (double*)out_sums, (double*)out_sumsq, out_segments, st)
+                                 : launch_pixels_reduce(off, num_jobs, q0, q1, c->d_px_samples, c->d_px_sseg, acc,
+                                                        (double*)out_sums, out_segments, st);
+                return pe;
+            });
+            if (rc) return rc;
         }
     }
     if (e != hipSuccess) return fail(c, RT_ERR_HIP, "pixel render launch: %s", hipGetErrorString(e));
@@ -1272,37 +1312,31 @@ int rt_render_pixels_moments(rt_ctx* c, const rt_camera* cam, const rt_pixel_job
                          out_sumsq, out_segments, stream);
 }
 
-// rt_render_pixels_aov: rt_render_pixels' checks, scan and scratch; one first-hit kernel in place
-// of the path kernel, the sums' seed and finalize launches once per summed output.
+// rt_render_pixels_aov: rt_render_pixels' prologue, scratch and passes; one first-hit kernel in
+// place of the path kernel, the sums' seed and finalize launches once per summed output.
 int rt_render_pixels_aov(rt_ctx* c, const rt_camera* cam, const rt_pixel_job* jobs, int num_jobs, int accumulate,
                          const rt_aov_buffers* out, void* stream) {
     const char* what = "rt_render_pixels_aov";
-    if (!c) return RT_ERR_INVALID;
-    if (!c->has_scene) return fail(c, RT_ERR_NO_SCENE, "%s before rt_upload_scene", what);
-    int rc = check_camera(c, cam);
-    if (rc) return rc;
-    if (num_jobs < 0 || (num_jobs > 0 && (!jobs || !out)))
-        return fail(c, RT_ERR_INVALID, "%s: %d jobs, jobs %p, out %p", what, num_jobs, (const void*)jobs,
-                    (const void*)out);
-    if (out && !out->albedo && !out->normal && !out->depth && !out->id && !out->hits)
-        return fail(c, RT_ERR_INVALID, "%s: every member of rt_aov_buffers is NULL", what);
-    const bool f64 = c->precision == RT_PREC_F64;
-    RenderParams P;
-    size_t lds;
-    if ((rc = query_setup(c, what, P, lds, cam))) return rc;
-    if (num_jobs == 0) return RT_OK;
+    JobQuery q;
+    int rc = job_query_begin(c, what, cam, jobs, num_jobs, stream, true, [&] {
+        if (num_jobs < 0 || (num_jobs > 0 && (!jobs || !out)))
+            return fail(c, RT_ERR_INVALID, "%s: %d jobs, jobs %p, out %p", what, num_jobs, (const void*)jobs,
+                        (const void*)out);
+        if (out && !out->albedo && !out->normal && !out->depth && !out->id && !out->hits)
+            return fail(c, RT_ERR_INVALID, "%s: every member of rt_aov_buffers is NULL", what);
+        return (int)RT_OK;
+    }, q);
+    if (rc || num_jobs == 0) return rc;
+    const RenderParams& P = q.P;
+    const size_t lds = q.lds, nj = (size_t)num_jobs;
+    const unsigned long long total = q.total;
+    const hipStream_t st = q.st;
     const rt_aov_buffers o = *out;
-    const size_t nj = (size_t)num_jobs;
     const int acc = accumulate ? 1 : 0;
-    hipStream_t st = stream ? (hipStream_t)stream : c->stream;
-    HIPCHK(c, hipEventRecord(c->ev0, st));
-    unsigned long long total = 0;
-    if ((rc = pixel_scan(c, cam, jobs, num_jobs, st, total))) return rc;
-    if (total > 0x7fffffffull) return fail(c, RT_ERR_LIMIT, "%s: %llu samples (> 2^31 - 1)", what, total);
     const unsigned long long* off = c->d_px_offsets;
     if ((rc = grow(c, &c->d_aov_near, &c->aov_near_cap, nj * 16))) return rc;
     hipError_t e = hipSuccess;
-    if (!f64) {
+    if (c->precision != RT_PREC_F64) {
         // albedo's sums and flags, then normal's, in rt_render_pixels' scratch
         if ((rc = grow(c, (void**)&c->d_px_acc, &c->px_acc_cap, nj * 6 * sizeof(long long)))) return rc;
         if ((rc = grow(c, (void**)&c->d_px_flags, &c->px_flags_cap, nj * 2 * sizeof(uint32_t)))) return rc;
@@ -1322,23 +1356,16 @@ int rt_render_pixels_aov(rt_ctx* c, const rt_camera* cam, const rt_pixel_job* jo
         if (e == hipSuccess && acc_n) e = launch_pixels_finalize(off, num_jobs, acc, acc_n, fl_n, (float*)o.normal, st);
         if (e == hipSuccess && near) e = launch_aov_finalize(off, num_jobs, acc, near, (float*)o.depth, o.id, st);
     } else {
-        // passes of at most floor(sample_buffer_mb 2^20 / 60) samples, reduced in order; the first
-        // one also fills the jobs without samples, so it runs even when T = 0
-        const unsigned long long fit = ((unsigned long long)c->tuning.sample_buffer_mb << 20) / AOV_SAMPLE_BYTES;
-        const unsigned long long pass = std::max(1ull, std::min(fit, total));
-        if ((rc = grow(c, (void**)&c->d_px_samples, &c->px_samples_cap, (size_t)pass * 7 * sizeof(double)))) return rc;
-        if ((rc = grow(c, (void**)&c->d_px_sseg, &c->px_sseg_cap, (size_t)pass * sizeof(int32_t)))) return rc;
-        unsigned long long q0 = 0;
-        do {
-            const unsigned long long q1 = std::min(total, q0 + pass);
-            e = launch_aov_f64(P, lds, st, jobs, off, num_jobs, total, q0, (int)(q1 - q0), c->d_remap, c->d_px_samples,
-                               (int32_t*)c->d_px_sseg, c->n_cu);
-            if (e == hipSuccess)
-                e = launch_aov_reduce(off, num_jobs, q0, q1, c->d_px_samples, (const int32_t*)c->d_px_sseg, acc,
-                                      c->d_aov_near, (double*)o.albedo, (double*)o.normal, (double*)o.depth, o.id,
-                                      o.hits, st);
-            q0 = q1;
-        } while (q0 < total && e == hipSuccess);
+        rc = sample_passes(c, total, AOV_SAMPLE_BYTES, e, [&](unsigned long long q0, unsigned long long q1) {
+            const hipError_t pe = launch_aov_f64(P, lds, st, jobs, off, num_jobs, total, q0, (int)(q1 - q0), c->d_remap,
+                                                 c->d_px_samples, (int32_t*)c->d_px_sseg, c->n_cu);
+            return pe != hipSuccess
+                       ? pe
+                       : launch_aov_reduce(off, num_jobs, q0, q1, c->d_px_samples, (const int32_t*)c->d_px_sseg, acc,
+                                           c->d_aov_near, (double*)o.albedo, (double*)o.normal, (double*)o.depth, o.id,
+                                           o.hits, st);
+        });
+        if (rc) return rc;
     }
     if (e != hipSuccess) return fail(c, RT_ERR_HIP, "aov launch: %s", hipGetErrorString(e));
     HIPCHK(c, hipEventRecord(c->ev1, st));

@@ -50,18 +50,6 @@ struct AovAcc {
     uint32_t* hits;               // num_jobs
 };
 
-// One channel of a sample onto the fixed-point grid (pixels_kernel's rule): the exact integer
-// in units of 2^-FIX_SHIFT, or 0 and a flag in fl.
-__device__ __forceinline__ long long aov_fix(float l, int c, uint32_t& fl) {
-    constexpr float SC = (float)(1 << FIX_SAMPLE_SHIFT), ISC = 1.f / SC;
-    const float v = __builtin_rintf(l * SC) * ISC;
-    if (v == 0.f) return 0;
-    const double q = (double)v * (double)(1ll << FIX_SHIFT);
-    if (fabs(q) < 0x1p62) return (long long)q;
-    fl |= (q != q ? FIX_NAN : q > 0 ? FIX_POS : FIX_NEG) << (3 * c);   // NaN, inf or overflow
-    return 0;
-}
-
 __device__ __forceinline__ unsigned long long aov_shfl_up(unsigned long long v, int d) {
     const uint32_t lo = (uint32_t)__shfl_up((int)(uint32_t)v, d), hi = (uint32_t)__shfl_up((int)(uint32_t)(v >> 32), d);
     return (unsigned long long)hi << 32 | lo;
@@ -96,13 +84,9 @@ __global__ __attribute__((amdgpu_flat_work_group_size(1, BLOCK), amdgpu_waves_pe
         double t = __builtin_huge_val();
         int32_t id = -1;
         if (valid) {
-            const unsigned long long fq = q_begin + i;
-            job = px_job_of(offsets, num_jobs, total, fq);
-            const PixelJob jb = jobs[job];
-            const uint32_t sample = jb.sample_begin + (uint32_t)(fq - offsets[job]);
             CounterRng rng;
-            rng.start(hash32(P.seed32 ^ jb.pixel), sample);
-            const Ray<R> ray = camera_ray<R>(P, (int)(jb.pixel % (uint32_t)P.W), (int)(jb.pixel / (uint32_t)P.W), rng);
+            Ray<R> ray;
+            job = px_sample_start<R>(P, jobs, offsets, num_jobs, total, q_begin + i, rng, ray);
             const Hit<R> h = closest_hit<R, EXACT, false, TRAV, MESH>(sc, ray, stack, BLOCK, NO_SELF, &dg);
             if (h.id != -1) {
                 const Shade<R> sh = shade<R, MESH>(sc, ray, h);
@@ -135,14 +119,14 @@ __global__ __attribute__((amdgpu_flat_work_group_size(1, BLOCK), amdgpu_waves_pe
             unsigned long long s[6] = {0, 0, 0, 0, 0, 0};   // (two's complement: sums wrap as the atomics do)
             if (hit) {
                 if (A.albedo) {
-                    s[0] = (unsigned long long)aov_fix(a.x, 0, fla);
-                    s[1] = (unsigned long long)aov_fix(a.y, 1, fla);
-                    s[2] = (unsigned long long)aov_fix(a.z, 2, fla);
+                    s[0] = (unsigned long long)fix_sample(a.x, 0, fla);
+                    s[1] = (unsigned long long)fix_sample(a.y, 1, fla);
+                    s[2] = (unsigned long long)fix_sample(a.z, 2, fla);
                 }
                 if (A.normal) {
-                    s[3] = (unsigned long long)aov_fix(nrm.x, 0, fln);
-                    s[4] = (unsigned long long)aov_fix(nrm.y, 1, fln);
-                    s[5] = (unsigned long long)aov_fix(nrm.z, 2, fln);
+                    s[3] = (unsigned long long)fix_sample(nrm.x, 0, fln);
+                    s[4] = (unsigned long long)fix_sample(nrm.y, 1, fln);
+                    s[5] = (unsigned long long)fix_sample(nrm.z, 2, fln);
                 }
             }
             if (fla) atomicOr(A.albedo_flags + job, fla);

@@ -225,6 +225,21 @@ constexpr int FIX_ITEM_SAMPLES = 32;         // <= 32 such values in [0, 1] sum 
 constexpr int FIX_LAUNCH_SAMPLES = 8191;     // a launch's packed sums stay below 2^32 per channel
 // accum_flags bits, per channel c at bit 3c: NaN, +overflow (+inf), -overflow (-inf)
 constexpr uint32_t FIX_NAN = 1u, FIX_POS = 2u, FIX_NEG = 4u;
+// One channel c of a sample onto the fixed-point grid, the rule of every per-job sum (rt_pixels.h,
+// rt_moments.h, rt_aov.h): render_lanes' rounding r = rintf(l 2^FIX_SAMPLE_SHIFT), then
+// flush_sample's 64-bit path -- the exact integer r 2^(FIX_SHIFT - FIX_SAMPLE_SHIFT), or 0 and
+// the channel's flag in fl (NaN, inf or overflow).  r_out: null, or where r itself goes.
+__device__ __forceinline__ long long fix_sample(float l, int c, uint32_t& fl, float* r_out = nullptr) {
+    constexpr float SC = (float)(1 << FIX_SAMPLE_SHIFT), ISC = 1.f / SC;
+    const float r = __builtin_rintf(l * SC);
+    if (r_out) *r_out = r;
+    const float v = r * ISC;
+    if (v == 0.f) return 0;
+    const double q = (double)v * (double)(1ll << FIX_SHIFT);
+    if (fabs(q) < 0x1p62) return (long long)q;
+    fl |= (q != q ? FIX_NAN : q > 0 ? FIX_POS : FIX_NEG) << (3 * c);
+    return 0;
+}
 constexpr int DIAG_SLOTS = 40;   // rt_render_diag_ex (RT_DIAG_SLOTS)
 
 // Coherent primaries (TRAV_COH, render_coherent): per wave, a FIFO of primary hits that

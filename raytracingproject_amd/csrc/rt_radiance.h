@@ -34,12 +34,16 @@ struct PathKey {   // = rt_path_key (include/rt_hip.h)
 };
 static_assert(sizeof(PathKey) == 16, "rt_path_key");
 
-// keys: n records, or null for {i, 0, 0} on ray i.  P.max_depth >= 1 (the C ABI answers
-// max_depth <= 0 without a launch).  segments: null, or n counts of closest_hit calls.
-template <class R, bool EXACT, int BLOCK, int MINW, int TRAV, bool MESH>
-__global__ __attribute__((amdgpu_flat_work_group_size(1, BLOCK), amdgpu_waves_per_eu(MINW))) void radiance_kernel(
-    RenderParams P, const R* __restrict__ rays, int n, const PathKey* __restrict__ keys, R* __restrict__ radiance,
-    uint32_t* __restrict__ segments) {
+// The persistent loop itself, shared by radiance_kernel, pixels_kernel (rt_pixels.h) and
+// pixels_moments_kernel (rt_moments.h): the scene load, the lane's path state, the claim from the
+// per-XCD heads of P.queue over indices [0, n), and the bounce loop in both arithmetics.  A
+// caller supplies the two places where the kernels differ:
+//   start(i, ray, rng)   the lane has claimed index i < n: set the path's first ray and start rng
+//                        on its stream (and keep what finish needs to know of i);
+//   finish(L, segs)      the path has ended with radiance L after segs closest_hit calls.
+// Both run under divergence, by the claiming / finishing lanes only.  P.max_depth >= 1.
+template <class R, bool EXACT, int BLOCK, int TRAV, bool MESH, class Start, class Finish>
+__device__ __forceinline__ void path_loop(const RenderParams& P, int n, Start&& start, Finish&& finish) {
     static_assert(!EXACT || sizeof(R) == 8, "EXACT needs fp64");
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     uint16_t* s_stack;
@@ -49,9 +53,7 @@ __global__ __attribute__((amdgpu_flat_work_group_size(1, BLOCK), amdgpu_waves_pe
     uint16_t* stack = s_stack + threadIdx.x;
     const int lane = threadIdx.x & 63;
 
-    // this lane's path: ray `idx` of the batch
-    int idx = 0;
-    bool live = false, fin = false;   // holds a path; the batch ran out for this lane
+    bool live = false, fin = false;   // holds a path; the indices ran out for this lane
     uint32_t segs = 0;
     CounterRng rng;
     rng.st = 0;
@@ -67,7 +69,7 @@ __global__ __attribute__((amdgpu_flat_work_group_size(1, BLOCK), amdgpu_waves_pe
     const uint32_t xcc = (uint32_t)__builtin_amdgcn_s_getreg(6164) & 7u;   // hwreg(HW_REG_XCC_ID, 0, 4)
     uint32_t hdone = 0;
     for (;;) {
-        // lanes without a path take the batch's next rays (the whole wave runs this)
+        // lanes without a path take the next indices (the whole wave runs this)
         bool need = !fin && !live;
         while (hdone < (uint32_t)QUEUE_HEADS) {
             const unsigned long long m = __ballot(need);
@@ -79,24 +81,12 @@ __global__ __attribute__((amdgpu_flat_work_group_size(1, BLOCK), amdgpu_waves_pe
             uint32_t base = 0;
             if (lane == __builtin_ctzll(__builtin_amdgcn_read_exec())) base = atomicAdd(P.queue + q * QUEUE_STRIDE, k);
             base = __builtin_amdgcn_readfirstlane(base);
-            // (64-bit: a head passes its last ray by at most 64 per wave of the grid, times 8)
+            // (64-bit: a head passes its last index by at most 64 per wave of the grid, times 8)
             const unsigned long long c = (unsigned long long)base + rank;
             const unsigned long long i = ((c >> 6) * QUEUE_HEADS + q) * 64 + (c & 63);
             const bool got = need && i < (unsigned long long)n;
             if (got) {
-                idx = (int)i;
-                const R* r7 = rays + (size_t)i * 7;
-                ray.o = mk(r7[0], r7[1], r7[2]);
-                ray.d = mk(r7[3], r7[4], r7[5]);
-                ray.time = r7[6];
-                uint32_t pixel = (uint32_t)i, sample = 0, first = 0;
-                if (keys) {
-                    pixel = keys[i].pixel;
-                    sample = keys[i].sample;
-                    first = keys[i].first_draw;
-                }
-                rng.start(hash32(P.seed32 ^ pixel), sample);
-                rng.skip(first);
+                start(i, ray, rng);
                 thr = mk((R)1, (R)1, (R)1);
                 nsc = 0;
                 self_id = NO_SELF;
@@ -138,15 +128,44 @@ __global__ __attribute__((amdgpu_flat_work_group_size(1, BLOCK), amdgpu_waves_pe
                 }
             }
             if (done) {
-                R* o = radiance + (size_t)idx * 3;
-                o[0] = L.x;
-                o[1] = L.y;
-                o[2] = L.z;
-                if (segments) segments[idx] = segs;
+                finish(L, segs);
                 live = false;
             }
         }
     }
+}
+
+// keys: n records, or null for {i, 0, 0} on ray i.  P.max_depth >= 1 (the C ABI answers
+// max_depth <= 0 without a launch).  segments: null, or n counts of closest_hit calls.
+template <class R, bool EXACT, int BLOCK, int MINW, int TRAV, bool MESH>
+__global__ __attribute__((amdgpu_flat_work_group_size(1, BLOCK), amdgpu_waves_per_eu(MINW))) void radiance_kernel(
+    RenderParams P, const R* __restrict__ rays, int n, const PathKey* __restrict__ keys, R* __restrict__ radiance,
+    uint32_t* __restrict__ segments) {
+    int idx = 0;   // this lane's path: ray `idx` of the batch
+    path_loop<R, EXACT, BLOCK, TRAV, MESH>(
+        P, n,
+        [&](unsigned long long i, Ray<R>& ray, CounterRng& rng) {
+            idx = (int)i;
+            const R* r7 = rays + (size_t)i * 7;
+            ray.o = mk(r7[0], r7[1], r7[2]);
+            ray.d = mk(r7[3], r7[4], r7[5]);
+            ray.time = r7[6];
+            uint32_t pixel = (uint32_t)i, sample = 0, first = 0;
+            if (keys) {
+                pixel = keys[i].pixel;
+                sample = keys[i].sample;
+                first = keys[i].first_draw;
+            }
+            rng.start(hash32(P.seed32 ^ pixel), sample);
+            rng.skip(first);
+        },
+        [&](const V3<R>& L, uint32_t segs) {
+            R* o = radiance + (size_t)idx * 3;
+            o[0] = L.x;
+            o[1] = L.y;
+            o[2] = L.z;
+            if (segments) segments[idx] = segs;
+        });
 }
 
 // The grid of a launch over n rays: one lane per ray up to the workgroups the device keeps
@@ -170,6 +189,25 @@ inline int radiance_grid(int v, size_t lds_bytes, int n, int n_cu) {
     const long resident = (long)wgs * (n_cu > 0 ? n_cu : 256);
     const long want = ((long)n + BLOCK - 1) / BLOCK;
     return (int)(want < resident ? want : resident);
+}
+
+// One launch of a kernel of this family over n indices: its VGPRs asked once, the grid that stays
+// resident, max_wgs > 0 (rt_tuning.grid_workgroups) a cap on it.
+template <auto KERNEL, int BLOCK, class... Args>
+inline hipError_t launch_resident(size_t lds_bytes, hipStream_t stream, int n, int n_cu, int max_wgs,
+                                  const Args&... args) {
+    static const int v = radiance_vgprs((const void*)KERNEL);
+    int grid = radiance_grid<BLOCK>(v, lds_bytes, n, n_cu);
+    if (max_wgs > 0 && grid > max_wgs) grid = max_wgs;
+    hipLaunchKernelGGL(KERNEL, dim3(grid), dim3(BLOCK), lds_bytes, stream, args...);
+    return hipGetLastError();
+}
+// ... of the mesh or the sphere instantiation, by the scene; P is the kernels' first argument.
+template <auto MESH_KERNEL, auto SPHERE_KERNEL, int BLOCK, class... Args>
+inline hipError_t launch_for_scene(const RenderParams& P, size_t lds_bytes, hipStream_t stream, int n, int n_cu,
+                                   int max_wgs, const Args&... args) {
+    return P.n_mnodes > 0 ? launch_resident<MESH_KERNEL, BLOCK>(lds_bytes, stream, n, n_cu, max_wgs, P, args...)
+                          : launch_resident<SPHERE_KERNEL, BLOCK>(lds_bytes, stream, n, n_cu, max_wgs, P, args...);
 }
 
 }  // namespace rtx

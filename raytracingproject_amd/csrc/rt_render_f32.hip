@@ -150,21 +150,9 @@ hipError_t launch_radiance_f32(const RenderParams& P, size_t lds_bytes, hipStrea
     if (n <= 0) return hipSuccess;
     constexpr int B = TRACE_BLOCK;
     constexpr int TS = TRAV_SELROOT | TRAV_B128 | TRAV_CULL, TM = TRAV_SELROOT | TRAV_CULL | TRAV_MIFIF;
-    const float* r = (const float*)rays;
-    const PathKey* k = (const PathKey*)keys;
-    float* o = (float*)radiance;
-    if (P.n_mnodes > 0) {
-        auto* kern = radiance_kernel<float, false, B, RADIANCE_MESH_WPE, TM, true>;
-        static const int v = radiance_vgprs((const void*)kern);
-        hipLaunchKernelGGL(kern, dim3(radiance_grid<B>(v, lds_bytes, n, n_cu)), dim3(B), lds_bytes, stream, P, r, n,
-                           k, o, segments);
-    } else {
-        auto* kern = radiance_kernel<float, false, B, RADIANCE_WPE, TS, false>;
-        static const int v = radiance_vgprs((const void*)kern);
-        hipLaunchKernelGGL(kern, dim3(radiance_grid<B>(v, lds_bytes, n, n_cu)), dim3(B), lds_bytes, stream, P, r, n,
-                           k, o, segments);
-    }
-    return hipGetLastError();
+    return launch_for_scene<radiance_kernel<float, false, B, RADIANCE_MESH_WPE, TM, true>,
+                            radiance_kernel<float, false, B, RADIANCE_WPE, TS, false>, B>(
+        P, lds_bytes, stream, n, n_cu, 0, (const float*)rays, n, (const PathKey*)keys, (float*)radiance, segments);
 }
 
 // Sparse rendering (rt_render_pixels), fp32: launch_radiance_f32's flags, register budgets and
@@ -176,19 +164,10 @@ hipError_t launch_pixels_f32(const RenderParams& P, size_t lds_bytes, hipStream_
     if (n <= 0) return hipSuccess;
     constexpr int B = TRACE_BLOCK;
     constexpr int TS = TRAV_SELROOT | TRAV_B128 | TRAV_CULL, TM = TRAV_SELROOT | TRAV_CULL | TRAV_MIFIF;
-    const PixelJob* j = (const PixelJob*)jobs;
-    if (P.n_mnodes > 0) {
-        auto* kern = pixels_kernel<float, false, B, RADIANCE_MESH_WPE, TM, true>;
-        static const int v = radiance_vgprs((const void*)kern);
-        hipLaunchKernelGGL(kern, dim3(radiance_grid<B>(v, lds_bytes, n, n_cu)), dim3(B), lds_bytes, stream, P, j,
-                           offsets, num_jobs, total, q_begin, n, acc, flags, segments, (float*)nullptr, (uint32_t*)nullptr);
-    } else {
-        auto* kern = pixels_kernel<float, false, B, RADIANCE_WPE, TS, false>;
-        static const int v = radiance_vgprs((const void*)kern);
-        hipLaunchKernelGGL(kern, dim3(radiance_grid<B>(v, lds_bytes, n, n_cu)), dim3(B), lds_bytes, stream, P, j,
-                           offsets, num_jobs, total, q_begin, n, acc, flags, segments, (float*)nullptr, (uint32_t*)nullptr);
-    }
-    return hipGetLastError();
+    return launch_for_scene<pixels_kernel<float, false, B, RADIANCE_MESH_WPE, TM, true>,
+                            pixels_kernel<float, false, B, RADIANCE_WPE, TS, false>, B>(
+        P, lds_bytes, stream, n, n_cu, 0, (const PixelJob*)jobs, offsets, num_jobs, total, q_begin, n, acc, flags,
+        segments, (float*)nullptr, (uint32_t*)nullptr);
 }
 
 // rt_render_pixels_moments, fp32: launch_pixels_f32's flags, register budgets and grid.
@@ -200,35 +179,24 @@ hipError_t launch_pixels_moments_f32(const RenderParams& P, size_t lds_bytes, hi
     if (n <= 0) return hipSuccess;
     constexpr int B = TRACE_BLOCK;
     constexpr int TS = TRAV_SELROOT | TRAV_B128 | TRAV_CULL, TM = TRAV_SELROOT | TRAV_CULL | TRAV_MIFIF;
-    const PixelJob* j = (const PixelJob*)jobs;
-    const auto cap = [max_wgs](int g) { return max_wgs > 0 && g > max_wgs ? max_wgs : g; };
-    if (P.n_mnodes > 0) {
-        auto* kern = pixels_moments_kernel<B, RADIANCE_MESH_WPE, TM, true>;
-        static const int v = radiance_vgprs((const void*)kern);
-        hipLaunchKernelGGL(kern, dim3(cap(radiance_grid<B>(v, lds_bytes, n, n_cu))), dim3(B), lds_bytes, stream, P, j,
-                           offsets, num_jobs, total, q_begin, n, acc, flags, segments, sq, sqflags);
-    } else {
-        auto* kern = pixels_moments_kernel<B, RADIANCE_WPE, TS, false>;
-        static const int v = radiance_vgprs((const void*)kern);
-        hipLaunchKernelGGL(kern, dim3(cap(radiance_grid<B>(v, lds_bytes, n, n_cu))), dim3(B), lds_bytes, stream, P, j,
-                           offsets, num_jobs, total, q_begin, n, acc, flags, segments, sq, sqflags);
-    }
-    return hipGetLastError();
+    return launch_for_scene<pixels_moments_kernel<B, RADIANCE_MESH_WPE, TM, true>,
+                            pixels_moments_kernel<B, RADIANCE_WPE, TS, false>, B>(
+        P, lds_bytes, stream, n, n_cu, max_wgs, (const PixelJob*)jobs, offsets, num_jobs, total, q_begin, n, acc, flags,
+        segments, sq, sqflags);
 }
 
 // First-hit auxiliary outputs (rt_render_pixels_aov), fp32: launch_trace_f32's traversal flags,
 // so a sample's record is rt_trace_rays'; launch_pixels_f32's register budgets and grid bound.
-template <bool MESH, bool COMBINE>
+template <bool COMBINE>
 static hipError_t launch_aov(const RenderParams& P, size_t lds_bytes, hipStream_t stream, const PixelJob* jobs,
                              const unsigned long long* offsets, int num_jobs, unsigned long long total,
                              const int* remap, const AovAcc& A, int n_cu) {
     constexpr int B = TRACE_BLOCK;
     constexpr int TS = TRAV_SELROOT | TRAV_B128 | TRAV_CULL, TM = TRAV_SELROOT | TRAV_CULL | TRAV_MIFIF;
-    auto* kern = aov_kernel<float, false, B, MESH ? RADIANCE_MESH_WPE : RADIANCE_WPE, MESH ? TM : TS, MESH, COMBINE>;
-    static const int v = radiance_vgprs((const void*)kern);
-    hipLaunchKernelGGL(kern, dim3(radiance_grid<B>(v, lds_bytes, (int)total, n_cu)), dim3(B), lds_bytes, stream, P,
-                       jobs, offsets, num_jobs, total, 0ull, (int)total, remap, A, (float*)nullptr, (int32_t*)nullptr);
-    return hipGetLastError();
+    return launch_for_scene<aov_kernel<float, false, B, RADIANCE_MESH_WPE, TM, true, COMBINE>,
+                            aov_kernel<float, false, B, RADIANCE_WPE, TS, false, COMBINE>, B>(
+        P, lds_bytes, stream, (int)total, n_cu, 0, jobs, offsets, num_jobs, total, 0ull, (int)total, remap, A,
+        (float*)nullptr, (int32_t*)nullptr);
 }
 
 hipError_t launch_aov_f32(const RenderParams& P, size_t lds_bytes, hipStream_t stream, const void* jobs,
@@ -238,11 +206,8 @@ hipError_t launch_aov_f32(const RenderParams& P, size_t lds_bytes, hipStream_t s
     if (total == 0) return hipSuccess;
     const PixelJob* j = (const PixelJob*)jobs;
     const AovAcc A{acc_albedo, flags_albedo, acc_normal, flags_normal, nearest, hits};
-    if (P.n_mnodes > 0)
-        return combine ? launch_aov<true, true>(P, lds_bytes, stream, j, offsets, num_jobs, total, remap, A, n_cu)
-                       : launch_aov<true, false>(P, lds_bytes, stream, j, offsets, num_jobs, total, remap, A, n_cu);
-    return combine ? launch_aov<false, true>(P, lds_bytes, stream, j, offsets, num_jobs, total, remap, A, n_cu)
-                   : launch_aov<false, false>(P, lds_bytes, stream, j, offsets, num_jobs, total, remap, A, n_cu);
+    return combine ? launch_aov<true>(P, lds_bytes, stream, j, offsets, num_jobs, total, remap, A, n_cu)
+                   : launch_aov<false>(P, lds_bytes, stream, j, offsets, num_jobs, total, remap, A, n_cu);
 }
 
 hipError_t launch_aov_seed(const unsigned long long* offsets, int num_jobs, int accumulate, const float* depth,

@@ -275,21 +275,9 @@ hipError_t launch_radiance_f64(const RenderParams& P, size_t lds_bytes, hipStrea
                                const void* keys, void* radiance, uint32_t* segments, int n_cu) {
     if (n <= 0) return hipSuccess;
     constexpr int B = TRACE_BLOCK;
-    const double* r = (const double*)rays;
-    const PathKey* k = (const PathKey*)keys;
-    double* o = (double*)radiance;
-    if (P.n_mnodes > 0) {
-        auto* kern = radiance_kernel<double, true, B, 4, TRAV_F32BOX, true>;
-        static const int v = radiance_vgprs((const void*)kern);
-        hipLaunchKernelGGL(kern, dim3(radiance_grid<B>(v, lds_bytes, n, n_cu)), dim3(B), lds_bytes, stream, P, r, n,
-                           k, o, segments);
-    } else {
-        auto* kern = radiance_kernel<double, true, B, 4, TRAV_F32BOX, false>;
-        static const int v = radiance_vgprs((const void*)kern);
-        hipLaunchKernelGGL(kern, dim3(radiance_grid<B>(v, lds_bytes, n, n_cu)), dim3(B), lds_bytes, stream, P, r, n,
-                           k, o, segments);
-    }
-    return hipGetLastError();
+    return launch_for_scene<radiance_kernel<double, true, B, 4, TRAV_F32BOX, true>,
+                            radiance_kernel<double, true, B, 4, TRAV_F32BOX, false>, B>(
+        P, lds_bytes, stream, n, n_cu, 0, (const double*)rays, n, (const PathKey*)keys, (double*)radiance, segments);
 }
 
 hipError_t launch_reconcile_accum(const float* out, long long* accum, uint32_t* flags, size_t npx,
@@ -336,30 +324,19 @@ hipError_t launch_pixels_f64(const RenderParams& P, size_t lds_bytes, hipStream_
                              double* samples, uint32_t* sample_segs, int n_cu, int max_wgs) {
     if (n <= 0) return hipSuccess;
     constexpr int B = TRACE_BLOCK;
-    const PixelJob* j = (const PixelJob*)jobs;
-    const auto cap = [max_wgs](int g) { return max_wgs > 0 && g > max_wgs ? max_wgs : g; };
-    if (P.n_mnodes > 0) {
-        auto* kern = pixels_kernel<double, true, B, 4, TRAV_F32BOX, true>;
-        static const int v = radiance_vgprs((const void*)kern);
-        hipLaunchKernelGGL(kern, dim3(cap(radiance_grid<B>(v, lds_bytes, n, n_cu))), dim3(B), lds_bytes, stream, P, j,
-                           offsets, num_jobs, total, q_begin, n, (unsigned long long*)nullptr, (uint32_t*)nullptr,
-                           (uint32_t*)nullptr, samples, sample_segs);
-    } else {
-        auto* kern = pixels_kernel<double, true, B, 4, TRAV_F32BOX, false>;
-        static const int v = radiance_vgprs((const void*)kern);
-        hipLaunchKernelGGL(kern, dim3(cap(radiance_grid<B>(v, lds_bytes, n, n_cu))), dim3(B), lds_bytes, stream, P, j,
-                           offsets, num_jobs, total, q_begin, n, (unsigned long long*)nullptr, (uint32_t*)nullptr,
-                           (uint32_t*)nullptr, samples, sample_segs);
-    }
-    return hipGetLastError();
+    return launch_for_scene<pixels_kernel<double, true, B, 4, TRAV_F32BOX, true>,
+                            pixels_kernel<double, true, B, 4, TRAV_F32BOX, false>, B>(
+        P, lds_bytes, stream, n, n_cu, max_wgs, (const PixelJob*)jobs, offsets, num_jobs, total, q_begin, n,
+        (unsigned long long*)nullptr, (uint32_t*)nullptr, (uint32_t*)nullptr, samples, sample_segs);
 }
 
 hipError_t launch_pixels_reduce(const unsigned long long* offsets, int num_jobs, unsigned long long q_begin,
                                 unsigned long long q_end, const double* samples, const uint32_t* sample_segs,
                                 int accumulate, double* out_sums, uint32_t* out_segments, hipStream_t stream) {
     if (num_jobs <= 0) return hipSuccess;
-    hipLaunchKernelGGL(pixels_reduce_kernel<double>, dim3((unsigned)((num_jobs + 255) / 256)), dim3(256), 0, stream,
-                       offsets, num_jobs, q_begin, q_end, samples, sample_segs, accumulate, out_sums, out_segments);
+    hipLaunchKernelGGL((pixels_reduce_kernel<double, false>), dim3((unsigned)((num_jobs + 255) / 256)), dim3(256), 0,
+                       stream, offsets, num_jobs, q_begin, q_end, samples, sample_segs, accumulate, out_sums,
+                       (double*)nullptr, out_segments);
     return hipGetLastError();
 }
 
@@ -422,20 +399,10 @@ hipError_t launch_aov_f64(const RenderParams& P, size_t lds_bytes, hipStream_t s
                           int n_cu) {
     if (n <= 0) return hipSuccess;
     constexpr int B = TRACE_BLOCK;
-    const PixelJob* j = (const PixelJob*)jobs;
-    const AovAcc none{};
-    if (P.n_mnodes > 0) {
-        auto* kern = aov_kernel<double, true, B, 4, TRAV_F32BOX, true, false>;
-        static const int v = radiance_vgprs((const void*)kern);
-        hipLaunchKernelGGL(kern, dim3(radiance_grid<B>(v, lds_bytes, n, n_cu)), dim3(B), lds_bytes, stream, P, j,
-                           offsets, num_jobs, total, q_begin, n, remap, none, records, record_ids);
-    } else {
-        auto* kern = aov_kernel<double, true, B, 4, TRAV_F32BOX, false, false>;
-        static const int v = radiance_vgprs((const void*)kern);
-        hipLaunchKernelGGL(kern, dim3(radiance_grid<B>(v, lds_bytes, n, n_cu)), dim3(B), lds_bytes, stream, P, j,
-                           offsets, num_jobs, total, q_begin, n, remap, none, records, record_ids);
-    }
-    return hipGetLastError();
+    return launch_for_scene<aov_kernel<double, true, B, 4, TRAV_F32BOX, true, false>,
+                            aov_kernel<double, true, B, 4, TRAV_F32BOX, false, false>, B>(
+        P, lds_bytes, stream, n, n_cu, 0, (const PixelJob*)jobs, offsets, num_jobs, total, q_begin, n, remap, AovAcc{},
+        records, record_ids);
 }
 
 hipError_t launch_aov_reduce(const unsigned long long* offsets, int num_jobs, unsigned long long q_begin,
@@ -455,7 +422,7 @@ hipError_t launch_pixels_reduce_moments(const unsigned long long* offsets, int n
                                         int accumulate, double* out_sums, double* out_sumsq, uint32_t* out_segments,
                                         hipStream_t stream) {
     if (num_jobs <= 0) return hipSuccess;
-    hipLaunchKernelGGL(pixels_reduce_moments_kernel<double>, dim3((unsigned)((num_jobs + 255) / 256)), dim3(256), 0,
+    hipLaunchKernelGGL((pixels_reduce_kernel<double, true>), dim3((unsigned)((num_jobs + 255) / 256)), dim3(256), 0,
                        stream, offsets, num_jobs, q_begin, q_end, samples, sample_segs, accumulate, out_sums, out_sumsq,
                        out_segments);
     return hipGetLastError();
