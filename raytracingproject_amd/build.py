@@ -34,7 +34,7 @@ UNITS = {
     "rt_lbvh.hip": ["-ffp-contract=off"],
     "rt_comm.cpp": [],
 }
-HEADERS = ["rt_device.h", "rt_render_impl.h", "rt_occluded.h", "rt_radiance.h", "rt_pixels.h", "rt_moments.h", "rt_aov.h", "rt_scene.h", "rt_launch.h", "rt_bvh.h", "rt_lbvh.h", "rt_ctx.h",
+HEADERS = ["rt_device.h", "rt_render_impl.h", "rt_occluded.h", "rt_radiance.h", "rt_pixels.h", "rt_moments.h", "rt_aov.h", "rt_scene.h", "rt_launch.h", "rt_bvh.h", "rt_lbvh.h", "rt_ctx.h", "rt_devbuf.h",
            "rt_treelet.h", "rt_pack.h", "rt_batch_cull.h"]
 
 
@@ -90,21 +90,12 @@ def build_dropin(verbose: bool = False) -> list[Path]:
     inc = ROOT / "include" / "rt"
     link = [f"-L{LIB.parent}", "-lrt_hip", f"-Wl,-rpath,{LIB.parent}", "-Wl,-rpath,$ORIGIN/../../raytracingproject_amd/lib"]
     built = []
-    exe = out_dir / "pixelmatch"
-    src = ROOT / "examples" / "pixelmatch.cpp"
-    if _stale(exe, [src, LIB, *inc.glob("*.h")]):
-        subprocess.run(["g++", "-O2", "-std=c++17", f"-I{inc}", str(src), "-o", str(exe), *link], check=True)
-    built.append(exe)
-    exe = out_dir / "host_queries"
-    src = ROOT / "examples" / "host_queries.cpp"
-    if _stale(exe, [src, LIB, *inc.glob("*.h")]):
-        subprocess.run(["g++", "-O2", "-std=c++17", f"-I{inc}", str(src), "-o", str(exe), *link], check=True)
-    built.append(exe)
-    exe = out_dir / "mesh_scene"
-    src = ROOT / "examples" / "mesh_scene.cpp"
-    if _stale(exe, [src, LIB, *inc.glob("*.h")]):
-        subprocess.run(["g++", "-O2", "-std=c++17", f"-I{inc}", str(src), "-o", str(exe), *link], check=True)
-    built.append(exe)
+    for name in ("pixelmatch", "host_queries", "mesh_scene"):
+        exe = out_dir / name
+        src = ROOT / "examples" / f"{name}.cpp"
+        if _stale(exe, [src, LIB, *inc.glob("*.h")]):
+            subprocess.run(["g++", "-O2", "-std=c++17", f"-I{inc}", str(src), "-o", str(exe), *link], check=True)
+        built.append(exe)
     ref_main = Path("/root/reference/src/main.cpp")
     if _present(ref_main):
         exe = out_dir / "reference_main_on_mi355x"
@@ -119,6 +110,19 @@ def build_dropin(verbose: bool = False) -> list[Path]:
 SAN_FLAGS = ["-O1", "-g", "-fno-omit-frame-pointer", "-fsanitize=address,undefined",
              "-fno-sanitize-recover=all"]
 SAN_EXE = OBJ / "san" / "san_driver"
+INC = f"-I{ROOT / 'include'}"
+
+
+def _build_san(exe: Path, srcs: list[Path], deps: list[Path], extra=(), verbose: bool = False) -> Path:
+    """One stand-alone g++ program under SAN_FLAGS: srcs (sources, or objects built before) with
+    `extra` flags into exe, when it is older than srcs, deps or this file.  No GPU code."""
+    exe.parent.mkdir(parents=True, exist_ok=True)
+    if _stale(exe, [*srcs, *deps, Path(__file__)]):
+        cmd = ["g++", "-std=c++17", *SAN_FLAGS, *extra, *map(str, srcs), "-o", str(exe), "-lm"]
+        if verbose:
+            print(" ".join(cmd), flush=True)
+        subprocess.run(cmd, check=True)
+    return exe
 
 
 def build_sanitize(verbose: bool = False) -> Path:
@@ -127,82 +131,55 @@ def build_sanitize(verbose: bool = False) -> Path:
     build the trees (csrc/rt_obj.cpp, csrc/rt_bvh.cpp) and the oracle (oracle/rt_oracle.c)
     compiled with g++/gcc -fsanitize=address,undefined into one driver,
     tests/cpp/sanitize_driver.cpp (run by tests/test_sanitize.py).  No GPU code."""
-    out = SAN_EXE.parent
-    out.mkdir(parents=True, exist_ok=True)
-    srcs = [ROOT / "tests" / "cpp" / "sanitize_driver.cpp", CSRC / "rt_obj.cpp", CSRC / "rt_bvh.cpp"]
-    orc = ROOT / "oracle" / "rt_oracle.c"
-    deps = srcs + [orc, CSRC / "rt_bvh.h", CSRC / "rt_scene.h", ROOT / "include" / "rt_hip.h",
-                   ROOT / "oracle" / "rt_oracle.h", Path(__file__)]
-    if _stale(SAN_EXE, deps):
-        oo = out / "rt_oracle.o"
+    SAN_EXE.parent.mkdir(parents=True, exist_ok=True)
+    orc, oo = ROOT / "oracle" / "rt_oracle.c", SAN_EXE.parent / "rt_oracle.o"
+    if _stale(oo, [orc, ROOT / "oracle" / "rt_oracle.h", Path(__file__)]):
         cmd = ["gcc", "-std=c11", *SAN_FLAGS, "-c", str(orc), "-o", str(oo)]
         if verbose:
             print(" ".join(cmd), flush=True)
         subprocess.run(cmd, check=True)
-        cmd = ["g++", "-std=c++17", *SAN_FLAGS, f"-I{ROOT / 'include'}", *map(str, srcs), str(oo), "-o",
-               str(SAN_EXE), "-lm"]
-        if verbose:
-            print(" ".join(cmd), flush=True)
-        subprocess.run(cmd, check=True)
-    return SAN_EXE
+    srcs = [ROOT / "tests" / "cpp" / "sanitize_driver.cpp", CSRC / "rt_obj.cpp", CSRC / "rt_bvh.cpp", oo]
+    deps = [CSRC / "rt_bvh.h", CSRC / "rt_scene.h", ROOT / "include" / "rt_hip.h", ROOT / "oracle" / "rt_oracle.h"]
+    return _build_san(SAN_EXE, srcs, deps, [INC], verbose)
 
 
 RESUME_EXE = OBJ / "san" / "grid_resume_driver"
+BOXES_EXE = OBJ / "san" / "bvh_boxes_driver"
+PACK_EXE = OBJ / "san" / "pack_driver"
+DEVBUF_EXE = OBJ / "san" / "devbuf_driver"
+BVH_DEPS = [CSRC / "rt_bvh.h", CSRC / "rt_scene.h", ROOT / "include" / "rt_hip.h"]
 
 
 def build_grid_resume(verbose: bool = False) -> Path:
     """tests/cpp/grid_resume_driver.cpp (the flat grid walk with suspension, restated for the
     CPU; run by tests/test_grid_resume.py) with csrc/rt_bvh.cpp, which builds its grids, under
     the same sanitizers as build_sanitize.  No GPU code."""
-    RESUME_EXE.parent.mkdir(parents=True, exist_ok=True)
     srcs = [ROOT / "tests" / "cpp" / "grid_resume_driver.cpp", CSRC / "rt_bvh.cpp"]
-    deps = srcs + [CSRC / "rt_bvh.h", CSRC / "rt_scene.h", ROOT / "include" / "rt_hip.h", Path(__file__)]
-    if _stale(RESUME_EXE, deps):
-        cmd = ["g++", "-std=c++17", *SAN_FLAGS, "-ffp-contract=off", f"-I{ROOT / 'include'}", *map(str, srcs), "-o",
-               str(RESUME_EXE), "-lm"]
-        if verbose:
-            print(" ".join(cmd), flush=True)
-        subprocess.run(cmd, check=True)
-    return RESUME_EXE
-
-
-BOXES_EXE = OBJ / "san" / "bvh_boxes_driver"
+    return _build_san(RESUME_EXE, srcs, BVH_DEPS, ["-ffp-contract=off", INC], verbose)
 
 
 def build_bvh_boxes(verbose: bool = False) -> Path:
     """tests/cpp/bvh_boxes_driver.cpp (the sphere tree's boxes and the sphere grid over scenes
     with negative radii; run by tests/test_bvh_boxes.py) with csrc/rt_bvh.cpp, which builds
     both, under the same sanitizers as build_sanitize.  No GPU code."""
-    BOXES_EXE.parent.mkdir(parents=True, exist_ok=True)
     srcs = [ROOT / "tests" / "cpp" / "bvh_boxes_driver.cpp", CSRC / "rt_bvh.cpp"]
-    deps = srcs + [CSRC / "rt_bvh.h", CSRC / "rt_scene.h", ROOT / "include" / "rt_hip.h", Path(__file__)]
-    if _stale(BOXES_EXE, deps):
-        cmd = ["g++", "-std=c++17", *SAN_FLAGS, "-ffp-contract=off", f"-I{ROOT / 'include'}", *map(str, srcs), "-o",
-               str(BOXES_EXE), "-lm"]
-        if verbose:
-            print(" ".join(cmd), flush=True)
-        subprocess.run(cmd, check=True)
-    return BOXES_EXE
-
-
-PACK_EXE = OBJ / "san" / "pack_driver"
+    return _build_san(BOXES_EXE, srcs, BVH_DEPS, ["-ffp-contract=off", INC], verbose)
 
 
 def build_pack(verbose: bool = False) -> Path:
     """tests/cpp/pack_driver.cpp (the host-side scene packing and the sphere grid's reach test;
     run by tests/test_pack.py) with csrc/rt_pack.cpp and csrc/rt_bvh.cpp, under the same
     sanitizers as build_sanitize.  No GPU code."""
-    PACK_EXE.parent.mkdir(parents=True, exist_ok=True)
     srcs = [ROOT / "tests" / "cpp" / "pack_driver.cpp", CSRC / "rt_pack.cpp", CSRC / "rt_bvh.cpp"]
-    deps = srcs + [CSRC / "rt_pack.h", CSRC / "rt_bvh.h", CSRC / "rt_scene.h", ROOT / "include" / "rt_hip.h",
-                   Path(__file__)]
-    if _stale(PACK_EXE, deps):
-        cmd = ["g++", "-std=c++17", *SAN_FLAGS, "-ffp-contract=off", f"-I{ROOT / 'include'}", *map(str, srcs), "-o",
-               str(PACK_EXE), "-lm"]
-        if verbose:
-            print(" ".join(cmd), flush=True)
-        subprocess.run(cmd, check=True)
-    return PACK_EXE
+    return _build_san(PACK_EXE, srcs, [CSRC / "rt_pack.h", *BVH_DEPS], ["-ffp-contract=off", INC], verbose)
+
+
+def build_devbuf(verbose: bool = False) -> Path:
+    """tests/cpp/devbuf_driver.cpp (csrc/rt_devbuf.h over counting fakes of the HIP calls it
+    makes; run by tests/test_devbuf.py), under the same sanitizers as build_sanitize.  Only
+    HIP's headers are used: no HIP library is linked, and no GPU code."""
+    extra = ["-D__HIP_PLATFORM_AMD__", f"-I{CSRC}", "-I/opt/rocm/include"]
+    return _build_san(DEVBUF_EXE, [ROOT / "tests" / "cpp" / "devbuf_driver.cpp"], [CSRC / "rt_devbuf.h"], extra, verbose)
 
 
 CULL_EXE = OBJ / "san" / "batch_cull_driver"
@@ -214,19 +191,13 @@ def build_batch_cull(verbose: bool = False) -> list[Path]:
     brute force over fp64 camera rays; run by tests/test_batch_cull.py) under the same sanitizers
     as build_sanitize: the driver itself, then one copy per mutation of the predicate, each of
     which the driver must catch.  No GPU code."""
-    CULL_EXE.parent.mkdir(parents=True, exist_ok=True)
     src = ROOT / "tests" / "cpp" / "batch_cull_driver.cpp"
-    deps = [src, CSRC / "rt_batch_cull.h", CSRC / "rt_scene.h", Path(__file__)]
+    deps = [CSRC / "rt_batch_cull.h", CSRC / "rt_scene.h"]
     exes = [CULL_EXE] + [CULL_EXE.with_name(f"batch_cull_driver_m{m}") for m in CULL_MUTANTS]
 
     def one(k: int) -> None:
-        if _stale(exes[k], deps):
-            # (-O2 after SAN_FLAGS' -O1: the brute force is a billion flops)
-            cmd = ["g++", "-std=c++17", *SAN_FLAGS, "-O2", "-ffp-contract=off", f"-DRT_CULL_MUTATE={k}", f"-I{CSRC}", str(src),
-                   "-o", str(exes[k]), "-lm"]
-            if verbose:
-                print(" ".join(cmd), flush=True)
-            subprocess.run(cmd, check=True)
+        # (-O2 after SAN_FLAGS' -O1: the brute force is a billion flops)
+        _build_san(exes[k], [src], deps, ["-O2", "-ffp-contract=off", f"-DRT_CULL_MUTATE={k}", f"-I{CSRC}"], verbose)
 
     with ThreadPoolExecutor(max_workers=4) as ex:
         list(ex.map(one, range(len(exes))))

@@ -17,6 +17,7 @@
 #include <cstring>
 #include <functional>
 #include <string>
+#include <utility>
 #include <vector>
 
 #include "../../include/rt_hip.h"
@@ -32,32 +33,18 @@ using namespace rtx_abi;
 
 namespace {
 
-void free_scene(rt_ctx* c) {
-    (void)hipFree(c->d_nodes);
-    (void)hipFree(c->d_sph);
-    (void)hipFree(c->d_mat);
-    (void)hipFree(c->d_big);
-    (void)hipFree(c->d_bigf);
-    c->d_bigf = nullptr;
-    (void)hipFree(c->d_mnodes);
-    (void)hipFree(c->d_tris);
-    (void)hipFree(c->d_tmeta);
-    (void)hipFree(c->d_remap);
-    c->d_remap = nullptr;
-    (void)hipFree(c->d_unmap);
-    c->d_unmap = nullptr;
-    c->n_unmap = 0;
-    (void)hipFree(c->d_grid);
-    c->d_grid = nullptr;
-    c->grid_nodes = c->grid_entries = 0;
-    c->d_mnodes = nullptr;
-    c->d_tris = nullptr;
-    c->d_tmeta = nullptr;
-    c->n_mnodes = c->n_tris = c->mdepth = c->mleaves = 0;
-    c->d_nodes = nullptr;
-    c->d_sph = c->d_mat = nullptr;
-    c->d_big = nullptr;
-    c->has_scene = false;
+void free_scene(rt_ctx* c) { c->scene = rt_ctx::Scene{}; }
+
+// the stream a call runs on: the caller's, or the context's
+hipStream_t stream_of(rt_ctx* c, void* stream) { return stream ? (hipStream_t)stream : c->stream; }
+
+// The end of a timed call, after its launches (e: the first error of them, reported under
+// `what`): ev1 on the stream, and the context has a time to report.
+int timed_end(rt_ctx* c, hipStream_t st, hipError_t e, const char* what) {
+    if (e != hipSuccess) return fail(c, RT_ERR_HIP, "%s: %s", what, hipGetErrorString(e));
+    HIPCHK(c, hipEventRecord(c->ev1, st));
+    c->timed = true;
+    return RT_OK;
 }
 
 size_t elem_bytes(const rt_ctx* c) { return c->precision == RT_PREC_F64 ? 8 : 4; }
@@ -66,17 +53,17 @@ size_t elem_bytes(const rt_ctx* c) { return c->precision == RT_PREC_F64 ? 8 : 4;
 // place (RenderParams::nodes / n_nodes), no traversal stack.
 void apply_grid(const rt_ctx* c, int tr, RenderParams& P) {
     if (!(tr & TRAV_GRID)) return;
-    P.nodes = (const Node*)c->d_grid;
-    P.n_nodes = c->grid_nodes;
+    P.nodes = (const Node*)c->scene.d_grid.p;
+    P.n_nodes = c->scene.grid_nodes;
     P.stack_size = 0;
-    P.grid = c->grid_hdr;
+    P.grid = c->scene.grid_hdr;
 }
 
 // the scene has a sphere grid and every ray a launch from cam can start lies within its
 // walk's reach (rt_pack.h grid_reach_ok: a host-side proof, made once per launch and handed
 // to the planner)
 bool grid_in_reach(const rt_ctx* c, const rt_camera* cam) {
-    return c->grid_nodes > 0 && grid_reach_ok(c->reach, c->grid_hdr.far_o, *cam);
+    return c->scene.grid_nodes > 0 && grid_reach_ok(c->scene.reach, c->scene.grid_hdr.far_o, *cam);
 }
 
 int check_camera(rt_ctx* c, const rt_camera* cam) {
@@ -119,24 +106,24 @@ void fill_params(const rt_ctx* c, const rt_camera* cam, int spp, int max_depth, 
     P.tiles_x = (P.W + 7) / 8;
     P.tiles_x_inv = 1.0 / P.tiles_x;
     P.tiles_x_inv_half = 0.5 * P.tiles_x_inv;
-    P.n_nodes = c->n_nodes;
-    P.n_spheres = c->n_sph;
-    P.n_mats = c->n_mat;
-    P.n_big = c->n_big;
-    P.n_front = c->n_front;
+    P.n_nodes = c->scene.n_nodes;
+    P.n_spheres = c->scene.n_sph;
+    P.n_mats = c->scene.n_mat;
+    P.n_big = c->scene.n_big;
+    P.n_front = c->scene.n_front;
     P.stack_size = stack_entries(c);
-    P.nodes = c->d_nodes;
-    P.spheres = c->d_sph;
-    P.mats = c->d_mat;
-    P.big = c->d_big;
-    P.bigf = c->d_bigf;
-    P.mnodes = c->d_mnodes;
-    P.tris = c->d_tris;
-    P.tmeta = c->d_tmeta;
-    P.n_mnodes = c->n_mnodes;
+    P.nodes = c->scene.d_nodes.as<Node>();
+    P.spheres = c->scene.d_sph.p;
+    P.mats = c->scene.d_mat.p;
+    P.big = c->scene.d_big.as<SphereD>();
+    P.bigf = c->scene.d_bigf.as<BigF>();
+    P.mnodes = c->scene.d_mnodes.as<Node4>();
+    P.tris = c->scene.d_tris.p;
+    P.tmeta = c->scene.d_tmeta.as<uint32_t>();
+    P.n_mnodes = c->scene.n_mnodes;
     P.mstack = mesh_stack;
-    P.box_extent = c->box_extent;
-    std::copy(c->mbox, c->mbox + 6, P.mbox);
+    P.box_extent = c->scene.box_extent;
+    std::copy(c->scene.mbox, c->scene.mbox + 6, P.mbox);
 }
 
 }  // namespace
@@ -211,85 +198,53 @@ rt_ctx* rt_create(int device, uint64_t seed, int precision) {
     if (hipGetDeviceCount(&n) != hipSuccess || device < 0 || device >= n) return nullptr;
     if (hipSetDevice(device) != hipSuccess) return nullptr;
     rt_ctx* c = new rt_ctx();
-    if (!parse_grid_suspend(getenv("RT_GRID_SUSPEND"), c->gsus_lanes, c->gsus_iters)) {
-        fprintf(stderr, "rt_create: RT_GRID_SUSPEND must be \"0\" or \"LANES,ITERS\" (1..64, 1..65535)\n");
-        delete c;
-        return nullptr;
-    }
-    if (!parse_batch_cull(getenv("RT_BATCH_CULL"), c->batch_cap)) {
-        fprintf(stderr, "rt_create: RT_BATCH_CULL must be 0..%d\n", BATCH_CAND_CAP);
-        delete c;
-        return nullptr;
-    }
-    if (!parse_batch_adopt(getenv("RT_BATCH_ADOPT"), c->batch_adopt)) {
-        fprintf(stderr, "rt_create: RT_BATCH_ADOPT must be 0 or 1\n");
-        delete c;
-        return nullptr;
-    }
-    // RT_AOV_COMBINE: "1" (rt_render_pixels_aov reduces a wave's lanes of one job before the
-    // atomics; the default, also unset or empty) or "0" (one set of atomics per sample).  The
-    // outputs do not depend on it.
-    if (!parse_batch_adopt(getenv("RT_AOV_COMBINE"), c->aov_combine)) {
-        fprintf(stderr, "rt_create: RT_AOV_COMBINE must be 0 or 1\n");
-        delete c;
-        return nullptr;
-    }
     c->device = device;
     c->seed = seed;
     c->precision = precision;
+    // RT_AOV_COMBINE: "1" (rt_render_pixels_aov reduces a wave's lanes of one job before the
+    // atomics; the default, also unset or empty) or "0" (one set of atomics per sample).  The
+    // outputs do not depend on it.
+    const struct {
+        bool ok;
+        const char* must;   // (a format of one int, BATCH_CAND_CAP)
+    } env[] = {
+        {parse_grid_suspend(getenv("RT_GRID_SUSPEND"), c->gsus_lanes, c->gsus_iters),
+         "rt_create: RT_GRID_SUSPEND must be \"0\" or \"LANES,ITERS\" (1..64, 1..65535)\n"},
+        {parse_batch_cull(getenv("RT_BATCH_CULL"), c->batch_cap), "rt_create: RT_BATCH_CULL must be 0..%d\n"},
+        {parse_batch_adopt(getenv("RT_BATCH_ADOPT"), c->batch_adopt), "rt_create: RT_BATCH_ADOPT must be 0 or 1\n"},
+        {parse_batch_adopt(getenv("RT_AOV_COMBINE"), c->aov_combine), "rt_create: RT_AOV_COMBINE must be 0 or 1\n"},
+    };
+    for (const auto& v : env)
+        if (!v.ok) {
+            fprintf(stderr, v.must, BATCH_CAND_CAP);
+            delete c;
+            return nullptr;
+        }
     if (hipDeviceGetAttribute(&c->n_cu, hipDeviceAttributeMultiprocessorCount, device) != hipSuccess) c->n_cu = 0;
     if (hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking) != hipSuccess ||
         hipEventCreate(&c->ev0) != hipSuccess || hipEventCreate(&c->ev1) != hipSuccess ||
-        hipMalloc((void**)&c->d_small, 16 * sizeof(double)) != hipSuccess ||
-        hipMalloc((void**)&c->d_used, sizeof(int)) != hipSuccess) {
-        rt_destroy(c);
+        c->d_small.reserve(16 * sizeof(double)) != hipSuccess || c->d_used.reserve(sizeof(int)) != hipSuccess) {
+        delete c;
         return nullptr;
     }
     return c;
 }
 
-void rt_destroy(rt_ctx* c) {
-    if (!c) return;
-    (void)hipSetDevice(c->device);
-    if (c->stream) (void)hipStreamSynchronize(c->stream);
-    free_scene(c);
-    (void)hipFree(c->d_shard);
-    (void)hipFree(c->d_frame);
-    (void)hipFree(c->d_segs);
-    (void)hipFree(c->d_segs_frame);
-    (void)hipFree(c->d_rgb);
-    (void)hipFree(c->d_tape);
-    (void)hipFree(c->d_small);
-    (void)hipFree(c->d_used);
-    (void)hipFree(c->d_samples);
-    (void)hipFree(c->d_queue64);
-    (void)hipFree(c->d_queue_rad);
-    (void)hipFree(c->d_px_offsets);
-    (void)hipFree(c->d_px_scan);
-    (void)hipFree(c->d_queue_px);
-    (void)hipFree(c->d_px_acc);
-    (void)hipFree(c->d_px_flags);
-    (void)hipFree(c->d_px_samples);
-    (void)hipFree(c->d_px_sseg);
-    (void)hipFree(c->d_px_sq);
-    (void)hipFree(c->d_px_sqflags);
-    (void)hipFree(c->d_aov_near);
-    (void)hipFree(c->d_gather);
-    for (auto& a : c->accum) {
-        (void)hipFree(a.acc);
-        (void)hipFree(a.accp);
-        (void)hipFree(a.flags);
-        (void)hipFree(a.queue);
-    }
-    (void)hipFree(c->d_rgb8);
-    if (c->h_pinned) (void)hipHostFree(c->h_pinned);
-    rt_comm_release(c);
-    c->lbvh.release();
-    if (c->ev0) (void)hipEventDestroy(c->ev0);
-    if (c->ev1) (void)hipEventDestroy(c->ev1);
-    if (c->stream) (void)hipStreamDestroy(c->stream);
-    delete c;
+// (the order: rt_ctx.h)
+rt_ctx::~rt_ctx() {
+    (void)hipSetDevice(device);
+    if (stream) (void)hipStreamSynchronize(stream);
+    if (h_pinned) (void)hipHostFree(h_pinned);
 }
+
+rt_ctx_base::~rt_ctx_base() {
+    rt_comm_release(this);
+    if (ev0) (void)hipEventDestroy(ev0);
+    if (ev1) (void)hipEventDestroy(ev1);
+    if (stream) (void)hipStreamDestroy(stream);
+}
+
+void rt_destroy(rt_ctx* c) { delete c; }
 
 const char* rt_last_error(const rt_ctx* c) { return c ? c->err.c_str() : "null context"; }
 
@@ -365,7 +320,7 @@ int rt_set_tuning(rt_ctx* c, const rt_tuning* t) {
                     t->block, t->waves_per_eu, t->traversal);
     const rt_tuning old = c->tuning;
     c->tuning = *t;
-    if (c->has_scene && plan_launch(c, true).lds_bytes > 160 * 1024) {
+    if (c->scene.has_scene && plan_launch(c, true).lds_bytes > 160 * 1024) {
         c->tuning = old;
         return fail(c, RT_ERR_LIMIT, "scene does not fit LDS at this block");
     }
@@ -425,52 +380,50 @@ int rt_upload_scene(rt_ctx* c, const rt_sphere* s, int n, const rt_material* m, 
     return rt_upload_scene_ex(c, s, n, m, nm, nullptr, 0);
 }
 
-// The packed scene onto the device (after free_scene), in the order of the records in
-// PackedScene; the mesh tree is uploaded, or built there from the caller's triangles.
-static int upload_packed(rt_ctx* c, PackedScene& pk, int n, const rt_material* m, int nm, const rt_triangle* tri,
-                         int ntri) {
+// The packed scene onto the device, into a scene record `s` of its own (the caller moves it
+// into the context once this has succeeded), in the order of the records in PackedScene; the
+// mesh tree is uploaded, or built there from the caller's triangles.
+static int upload_packed(rt_ctx* c, rt_ctx::Scene& s, PackedScene& pk, int n, const rt_material* m, int nm,
+                         const rt_triangle* tri, int ntri) {
     const bool f64 = pk.f64;
-    auto upload = [&](void** dst, const void* src, size_t bytes) -> int {
-        HIPCHK(c, hipMalloc(dst, bytes ? bytes : 16));
-        if (bytes) HIPCHK(c, hipMemcpy(*dst, src, bytes, hipMemcpyHostToDevice));
+    auto upload = [&](DevBuf& dst, const void* src, size_t bytes) -> int {
+        HIPCHK(c, dst.reserve(bytes));
+        if (bytes) HIPCHK(c, hipMemcpy(dst.p, src, bytes, hipMemcpyHostToDevice));
         return RT_OK;
     };
     int rc;
-    if ((rc = upload((void**)&c->d_nodes, pk.bvh.nodes.data(), pk.bvh.nodes.size() * sizeof(Node))) != RT_OK) return rc;
-    if ((rc = f64 ? upload(&c->d_sph, pk.sd.data(), pk.sd.size() * sizeof(SphereD))
-                  : upload(&c->d_sph, pk.sf.data(), pk.sf.size() * sizeof(SphereF))) != RT_OK)
+    if ((rc = upload(s.d_nodes, pk.bvh.nodes.data(), pk.bvh.nodes.size() * sizeof(Node))) != RT_OK) return rc;
+    if ((rc = f64 ? upload(s.d_sph, pk.sd.data(), pk.sd.size() * sizeof(SphereD))
+                  : upload(s.d_sph, pk.sf.data(), pk.sf.size() * sizeof(SphereF))) != RT_OK)
         return rc;
-    if ((rc = f64 ? upload(&c->d_mat, pk.md.data(), pk.md.size() * sizeof(MatD))
-                  : upload(&c->d_mat, pk.mf.data(), pk.mf.size() * sizeof(MatF))) != RT_OK)
+    if ((rc = f64 ? upload(s.d_mat, pk.md.data(), pk.md.size() * sizeof(MatD))
+                  : upload(s.d_mat, pk.mf.data(), pk.mf.size() * sizeof(MatF))) != RT_OK)
         return rc;
     if (!pk.grid.empty()) {
-        if ((rc = upload(&c->d_grid, pk.grid.data(), pk.grid.size())) != RT_OK) return rc;
-        c->grid_nodes = (int)(pk.grid.size() / sizeof(Node));
-        c->grid_hdr = pk.grid_hdr;
-        c->grid_density = c->tuning.sphere_grid_density;
-        c->grid_entries = pk.grid_entries;
+        if ((rc = upload(s.d_grid, pk.grid.data(), pk.grid.size())) != RT_OK) return rc;
+        s.grid_nodes = (int)(pk.grid.size() / sizeof(Node));
+        s.grid_hdr = pk.grid_hdr;
+        s.grid_density = c->tuning.sphere_grid_density;
+        s.grid_entries = pk.grid_entries;
     }
-    if ((rc = upload((void**)&c->d_big, pk.big.data(), pk.big.size() * sizeof(SphereD))) != RT_OK) return rc;
-    if ((rc = upload((void**)&c->d_bigf, pk.bigf.data(), pk.bigf.size() * sizeof(BigF))) != RT_OK) return rc;
+    if ((rc = upload(s.d_big, pk.big.data(), pk.big.size() * sizeof(SphereD))) != RT_OK) return rc;
+    if ((rc = upload(s.d_bigf, pk.bigf.data(), pk.bigf.size() * sizeof(BigF))) != RT_OK) return rc;
     if (pk.gpu_build) {
-        rt_triangle* d_in = nullptr;
-        uint32_t* d_types = nullptr;
+        DevBuf d_in, d_types;
         std::vector<uint32_t> types(nm);
         for (int k = 0; k < nm; ++k) types[k] = (uint32_t)m[k].type;
-        if ((rc = upload((void**)&d_in, tri, (size_t)ntri * sizeof(rt_triangle))) != RT_OK) return rc;
-        if ((rc = upload((void**)&d_types, types.data(), types.size() * 4)) != RT_OK) {
-            (void)hipFree(d_in);
-            return rc;
-        }
+        if ((rc = upload(d_in, tri, (size_t)ntri * sizeof(rt_triangle))) != RT_OK) return rc;
+        if ((rc = upload(d_types, types.data(), types.size() * 4)) != RT_OK) return rc;
         const int cap = ntri > 1 ? ntri - 1 : 1;
-        hipError_t e = hipMalloc((void**)&c->d_mnodes, (size_t)cap * sizeof(Node4));
-        if (e == hipSuccess) e = hipMalloc(&c->d_tris, f64 ? (size_t)ntri * sizeof(TriD) : (size_t)ntri * sizeof(TriF) + TRIF_SLACK);
-        if (e == hipSuccess && !f64) e = hipMalloc((void**)&c->d_tmeta, (size_t)ntri * sizeof(uint32_t));
-        if (e == hipSuccess && !f64) e = hipMemsetAsync((char*)c->d_tris + (size_t)ntri * sizeof(TriF), 0, TRIF_SLACK, c->stream);
+        hipError_t e = s.d_mnodes.reserve((size_t)cap * sizeof(Node4));
+        if (e == hipSuccess) e = s.d_tris.reserve(f64 ? (size_t)ntri * sizeof(TriD) : (size_t)ntri * sizeof(TriF) + TRIF_SLACK);
+        if (e == hipSuccess && !f64) e = s.d_tmeta.reserve((size_t)ntri * sizeof(uint32_t));
+        if (e == hipSuccess && !f64)
+            e = hipMemsetAsync(s.d_tris.as<char>() + (size_t)ntri * sizeof(TriF), 0, TRIF_SLACK, c->stream);
         LbvhInput in{};
-        in.tris = d_in;
+        in.tris = d_in.as<rt_triangle>();
         in.n = ntri;
-        in.mat_type = d_types;
+        in.mat_type = d_types.as<uint32_t>();
         for (int a = 0; a < 3; ++a) {
             in.lo[a] = pk.clo[a];
             in.inv[a] = pk.chi[a] > pk.clo[a] ? 1.0 / (pk.chi[a] - pk.clo[a]) : 0.0;
@@ -480,38 +433,36 @@ static int upload_packed(rt_ctx* c, PackedScene& pk, int n, const rt_material* m
         // two rounds of treelet restructuring: the 4-wide SAH cost of the C4 blob's tree 28.56
         // -> 25.77 -> 25.41 (3: 25.32) against the host SAH tree's 24.7 (tests/cpp/treelet_check.cpp)
         in.treelet_rounds = c->tuning.mesh_builder == RT_MESH_BUILD_GPU ? 2 : 0;
-        LbvhOutput out{c->d_mnodes, cap, c->d_tris, c->d_tmeta};
+        LbvhOutput out{s.d_mnodes.as<Node4>(), cap, s.d_tris.p, s.d_tmeta.as<uint32_t>()};
         if (e == hipSuccess) e = lbvh_build(in, c->lbvh, out, c->stream);
-        (void)hipFree(d_in);
-        (void)hipFree(d_types);
         if (e != hipSuccess) return fail(c, RT_ERR_HIP, "GPU mesh BVH build: %s", hipGetErrorString(e));
         if (3 * out.depth4 + 1 > MESH_STACK_MAX)
             return fail(c, RT_ERR_LIMIT, "GPU mesh BVH depth %d exceeds the traversal stack (use the host builder)",
                         out.depth4);
-        c->n_mnodes = out.node_count;
-        c->n_tris = ntri;
-        c->mdepth = out.depth4;
-        c->mleaves = out.leaves;
+        s.n_mnodes = out.node_count;
+        s.n_tris = ntri;
+        s.mdepth = out.depth4;
+        s.mleaves = out.leaves;
     } else if (ntri > 0) {
         const MeshBvh& mbvh = pk.mbvh;
-        if ((rc = upload((void**)&c->d_mnodes, mbvh.nodes4.data(), mbvh.nodes4.size() * sizeof(Node4))) != RT_OK)
+        if ((rc = upload(s.d_mnodes, mbvh.nodes4.data(), mbvh.nodes4.size() * sizeof(Node4))) != RT_OK)
             return rc;
         if (f64) {
-            if ((rc = upload(&c->d_tris, pk.td.data(), pk.td.size() * sizeof(TriD))) != RT_OK) return rc;
+            if ((rc = upload(s.d_tris, pk.td.data(), pk.td.size() * sizeof(TriD))) != RT_OK) return rc;
         } else {
-            if ((rc = upload(&c->d_tris, pk.tf.data(), pk.tf.size() * sizeof(TriF))) != RT_OK) return rc;
-            if ((rc = upload((void**)&c->d_tmeta, pk.tmeta.data(), pk.tmeta.size() * sizeof(uint32_t))) != RT_OK) return rc;
+            if ((rc = upload(s.d_tris, pk.tf.data(), pk.tf.size() * sizeof(TriF))) != RT_OK) return rc;
+            if ((rc = upload(s.d_tmeta, pk.tmeta.data(), pk.tmeta.size() * sizeof(uint32_t))) != RT_OK) return rc;
         }
-        c->n_mnodes = (int)mbvh.nodes4.size();
-        c->n_tris = ntri;
-        c->mdepth = mbvh.depth4;
-        c->mleaves = mbvh.leaves;
+        s.n_mnodes = (int)mbvh.nodes4.size();
+        s.n_tris = ntri;
+        s.mdepth = mbvh.depth4;
+        s.mleaves = mbvh.leaves;
     }
-    if (c->n_mnodes > 0) {
+    if (s.n_mnodes > 0) {
         // the mesh's box: the union of the root's child boxes, as the kernels test them
         // (read back from the device, so either builder's tree gives it)
         Node4 root;
-        const hipError_t e = hipMemcpy(&root, c->d_mnodes, sizeof(Node4), hipMemcpyDeviceToHost);
+        const hipError_t e = hipMemcpy(&root, s.d_mnodes.p, sizeof(Node4), hipMemcpyDeviceToHost);
         if (e != hipSuccess) return fail(c, RT_ERR_HIP, "mesh root read-back: %s", hipGetErrorString(e));
         const float inf = std::numeric_limits<float>::infinity();
         float b[6] = {inf, inf, inf, -inf, -inf, -inf};
@@ -520,7 +471,7 @@ static int upload_packed(rt_ctx* c, PackedScene& pk, int n, const rt_material* m
             b[0] = std::min(b[0], root.lox[k]), b[1] = std::min(b[1], root.loy[k]), b[2] = std::min(b[2], root.loz[k]);
             b[3] = std::max(b[3], root.hix[k]), b[4] = std::max(b[4], root.hiy[k]), b[5] = std::max(b[5], root.hiz[k]);
         }
-        std::copy(b, b + 6, c->mbox);
+        std::copy(b, b + 6, s.mbox);
     }
     if (pk.gpu_build) {
         // rt_trace_rays' id map, the triangle part: the device builder's leaf order
@@ -529,22 +480,19 @@ static int upload_packed(rt_ctx* c, PackedScene& pk, int n, const rt_material* m
         for (uint32_t k : perm) pk.remap.push_back(n + (int)k);
         invert_remap(pk.remap, (int)pk.bvh.order.size(), (int)pk.big.size(), n + ntri, pk.unmap);
     }
-    if ((rc = upload((void**)&c->d_remap, pk.remap.data(), pk.remap.size() * sizeof(int))) != RT_OK) return rc;
-    if ((rc = upload((void**)&c->d_unmap, pk.unmap.data(), pk.unmap.size() * sizeof(int))) != RT_OK) return rc;
-    c->n_unmap = (int)pk.unmap.size();
-    c->box_extent = pk.box_extent;
-    c->reach = pk.reach;
-    c->n_nodes = (int)pk.bvh.nodes.size();
-    c->n_sph = (int)pk.bvh.order.size();
-    c->n_front = pk.bvh.front;
-    c->n_mat = nm;
-    c->n_big = (int)pk.big.size();
-    c->depth = pk.bvh.depth;
-    c->leaves = pk.bvh.leaves;
-    c->n_input = n;
-    const size_t lds = plan_launch(c, true).lds_bytes;
-    if (lds > 160 * 1024) return fail(c, RT_ERR_LIMIT, "scene needs %zu B of LDS per workgroup (> 160 KiB)", lds);
-    c->has_scene = true;
+    if ((rc = upload(s.d_remap, pk.remap.data(), pk.remap.size() * sizeof(int))) != RT_OK) return rc;
+    if ((rc = upload(s.d_unmap, pk.unmap.data(), pk.unmap.size() * sizeof(int))) != RT_OK) return rc;
+    s.n_unmap = (int)pk.unmap.size();
+    s.box_extent = pk.box_extent;
+    s.reach = pk.reach;
+    s.n_nodes = (int)pk.bvh.nodes.size();
+    s.n_sph = (int)pk.bvh.order.size();
+    s.n_front = pk.bvh.front;
+    s.n_mat = nm;
+    s.n_big = (int)pk.big.size();
+    s.depth = pk.bvh.depth;
+    s.leaves = pk.bvh.leaves;
+    s.n_input = n;
     return RT_OK;
 }
 
@@ -556,20 +504,31 @@ int rt_upload_scene_ex(rt_ctx* c, const rt_sphere* s, int n, const rt_material* 
     int rc = pack_scene(s, n, m, nm, tri, ntri, c->tuning, c->precision == RT_PREC_F64, pk, err);
     if (rc != RT_OK) return fail(c, rc, "%s", err.c_str());
     HIPCHK(c, hipSetDevice(c->device));
+    // from here on the old scene is gone (its memory is free for the new one's); the new one
+    // is the context's only once it is whole, and only where a launch of it fits LDS (the plan
+    // reads the context, so that one check follows the move and takes the scene back out)
     free_scene(c);
-    if ((rc = upload_packed(c, pk, n, m, nm, tri, ntri)) != RT_OK) free_scene(c);
-    return rc;
+    rt_ctx::Scene up;
+    if ((rc = upload_packed(c, up, pk, n, m, nm, tri, ntri)) != RT_OK) return rc;
+    c->scene = std::move(up);
+    const size_t lds = plan_launch(c, true).lds_bytes;
+    if (lds > 160 * 1024) {
+        free_scene(c);
+        return fail(c, RT_ERR_LIMIT, "scene needs %zu B of LDS per workgroup (> 160 KiB)", lds);
+    }
+    c->scene.has_scene = true;
+    return RT_OK;
 }
 
 int rt_scene_info_get(rt_ctx* c, rt_scene_info* info) {
     if (!c || !info) return RT_ERR_INVALID;
-    if (!c->has_scene) return fail(c, RT_ERR_NO_SCENE, "no scene");
-    info->num_spheres = c->n_input;
-    info->num_materials = c->n_mat;
-    info->bvh_nodes = c->n_nodes;
-    info->bvh_depth = c->depth;
-    info->bvh_leaves = c->leaves;
-    info->big_spheres = c->n_big;
+    if (!c->scene.has_scene) return fail(c, RT_ERR_NO_SCENE, "no scene");
+    info->num_spheres = c->scene.n_input;
+    info->num_materials = c->scene.n_mat;
+    info->bvh_nodes = c->scene.n_nodes;
+    info->bvh_depth = c->scene.depth;
+    info->bvh_leaves = c->scene.leaves;
+    info->big_spheres = c->scene.n_big;
     // (the plan of a launch whose rays all start within the sphere grid's reach: rt_grid_reach)
     const LaunchPlan plan = plan_launch(c, true);
     info->lds_bytes = (int)plan.lds_bytes;
@@ -577,22 +536,22 @@ int rt_scene_info_get(rt_ctx* c, rt_scene_info* info) {
     info->render_traversal = plan.trav;
     info->render_waves_per_eu = plan.wpe;
     info->render_mesh_lds_stack = plan.mesh_stack;
-    for (int a = 0; a < 3; ++a) info->grid_res[a] = c->grid_nodes > 0 ? c->grid_hdr.res[a] : 0;
-    info->grid_entries = c->grid_entries;
-    info->grid_time_slabs = c->grid_nodes > 0 ? c->grid_hdr.n_slab : 0;
-    info->grid_far_o = c->grid_nodes > 0 ? c->grid_hdr.far_o : 0.f;
-    info->grid_density = c->grid_nodes > 0 ? c->grid_density : 0.0;
+    for (int a = 0; a < 3; ++a) info->grid_res[a] = c->scene.grid_nodes > 0 ? c->scene.grid_hdr.res[a] : 0;
+    info->grid_entries = c->scene.grid_entries;
+    info->grid_time_slabs = c->scene.grid_nodes > 0 ? c->scene.grid_hdr.n_slab : 0;
+    info->grid_far_o = c->scene.grid_nodes > 0 ? c->scene.grid_hdr.far_o : 0.f;
+    info->grid_density = c->scene.grid_nodes > 0 ? c->scene.grid_density : 0.0;
     info->precision = c->precision;
-    info->num_triangles = c->n_tris;
-    info->mesh_nodes = c->n_mnodes;
-    info->mesh_depth = c->mdepth;
-    info->mesh_leaves = c->mleaves;
+    info->num_triangles = c->scene.n_tris;
+    info->mesh_nodes = c->scene.n_mnodes;
+    info->mesh_depth = c->scene.mdepth;
+    info->mesh_leaves = c->scene.mleaves;
     return RT_OK;
 }
 
 int rt_grid_reach(rt_ctx* c, const rt_camera* cam, int32_t* walks) {
     if (!c || !walks) return RT_ERR_INVALID;
-    if (!c->has_scene) return fail(c, RT_ERR_NO_SCENE, "rt_grid_reach before rt_upload_scene");
+    if (!c->scene.has_scene) return fail(c, RT_ERR_NO_SCENE, "rt_grid_reach before rt_upload_scene");
     int rc = check_camera(c, cam);
     if (rc) return rc;
     *walks = grid_in_reach(c, cam) ? 1 : 0;
@@ -623,7 +582,7 @@ int rt_shard_layout(int width, int height, int shard, int num_shards, rt_shard_i
 // profiles/r02/item_cap_scaling_r02bn.log; 4 at 8 GPUs lost, item_size_sweep_r02ai.log)
 static int item_cap(const rt_ctx* c, int trav, double lanes, double pixels) {
     int cmax = std::min(c->tuning.item_samples, FIX_ITEM_SAMPLES);
-    if ((trav & TRAV_COH) && c->n_mnodes == 0) {
+    if ((trav & TRAV_COH) && c->scene.n_mnodes == 0) {
         const double ppl = pixels / std::max(1.0, lanes);
         int cap = 1, floor_cap = 1;
         while (cap * 2 <= 12.0 * ppl && cap < FIX_ITEM_SAMPLES) cap *= 2;
@@ -665,18 +624,15 @@ static void plan_phases(RenderParams& P, int spp, double lanes, double pixels, d
 // N = 1 frames of 37.14 / 37.22 / 37.67 / 37.99 ms).  Sphere scenes were not measured this
 // way and keep item_balance.
 static double item_balance_of(const rt_ctx* c, double lanes, double pixels) {
-    if (c->n_mnodes == 0) return c->tuning.item_balance;
+    if (c->scene.n_mnodes == 0) return c->tuning.item_balance;
     return c->tuning.mesh_item_balance * (lanes > pixels ? 2.0 : 1.0);
-}
-
-static int launch_rc(rt_ctx* c, hipError_t e) {
-    return e == hipSuccess ? RT_OK : fail(c, RT_ERR_HIP, "render launch: %s", hipGetErrorString(e));
 }
 
 // One fp32 launch of P.spp <= FIX_LAUNCH_SAMPLES samples from P.sample_begin: lanes add their
 // chunk's fixed-point sums into the context's accumulator for this buffer (integer atomics:
-// order-free), finalize_kernel writes out_sums.
-static int render_range_f32(rt_ctx* c, const LaunchPlan& plan, RenderParams P, size_t npx, hipStream_t st) {
+// order-free), finalize_kernel writes out_sums.  e: the first launch error.
+static int render_range_f32(rt_ctx* c, const LaunchPlan& plan, RenderParams P, size_t npx, hipStream_t st,
+                            hipError_t& e) {
     float* out_sums = (float*)P.out_sums;
     int rc;
     rt_ctx::Accum* slot = nullptr;
@@ -688,55 +644,58 @@ static int render_range_f32(rt_ctx* c, const LaunchPlan& plan, RenderParams P, s
         for (auto& a : c->accum)
             if (a.used < slot->used) slot = &a;
     }
-    if ((rc = grow(c, (void**)&slot->acc, &slot->acc_cap, npx * 3 * sizeof(long long)))) return rc;
-    if ((rc = grow(c, (void**)&slot->accp, &slot->accp_cap, npx * 2 * sizeof(unsigned long long)))) return rc;
-    if ((rc = grow(c, (void**)&slot->flags, &slot->flags_cap, npx * sizeof(uint32_t)))) return rc;
+    if ((rc = reserve(c, slot->acc, npx * 3 * sizeof(long long)))) return rc;
+    if ((rc = reserve(c, slot->accp, npx * 2 * sizeof(unsigned long long)))) return rc;
+    if ((rc = reserve(c, slot->flags, npx * sizeof(uint32_t)))) return rc;
     slot->out = out_sums;
     slot->W = P.W;
     slot->H = P.H;
     slot->shard = P.shard;
     slot->nshards = P.nshards;
     slot->used = ++c->accum_clock;
-    P.accum = slot->acc;
-    P.accum_flags = slot->flags;
-    P.accp = slot->accp;
+    long long* acc = slot->acc.as<long long>();
+    unsigned long long* accp = slot->accp.as<unsigned long long>();
+    uint32_t* flags = slot->flags.as<uint32_t>();
+    P.accum = acc;
+    P.accum_flags = flags;
+    P.accp = accp;
     P.diag = c->diag_buf;
     P.gsus_lanes = c->gsus_lanes;
     P.gsus_iters = c->gsus_iters;
     P.batch_cap = c->batch_cap;
     P.batch_adopt = c->batch_adopt;
-    if (!slot->queue) HIPCHK(c, hipMalloc((void**)&slot->queue, QUEUE_CTRL_BYTES));
-    P.queue = slot->queue;
+    HIPCHK(c, slot->queue.reserve(QUEUE_CTRL_BYTES));
+    P.queue = slot->queue.as<uint32_t>();
     {
         const double lanes = (double)P.max_wgs * plan.block, pixels = (double)npx;
         plan_phases(P, P.spp, lanes, pixels, item_balance_of(c, lanes, pixels), item_cap(c, plan.trav, lanes, pixels));
     }
-    HIPCHK(c, hipMemsetAsync(slot->queue, 0, QUEUE_CTRL_BYTES, st));
-    HIPCHK(c, hipMemsetAsync(slot->accp, 0, npx * 2 * sizeof(unsigned long long), st));
-    hipError_t e = hipSuccess;
+    HIPCHK(c, hipMemsetAsync(P.queue, 0, QUEUE_CTRL_BYTES, st));
+    HIPCHK(c, hipMemsetAsync(accp, 0, npx * 2 * sizeof(unsigned long long), st));
     if (!P.accumulate) {
-        e = hipMemsetAsync(slot->acc, 0, npx * 3 * sizeof(long long), st);
-        if (e == hipSuccess) e = hipMemsetAsync(slot->flags, 0, npx * sizeof(uint32_t), st);
+        e = hipMemsetAsync(acc, 0, npx * 3 * sizeof(long long), st);
+        if (e == hipSuccess) e = hipMemsetAsync(flags, 0, npx * sizeof(uint32_t), st);
         if (e == hipSuccess && P.out_segs) e = hipMemsetAsync(P.out_segs, 0, npx * sizeof(uint32_t), st);
     } else if (!have) {
         // no fixed-point state for this buffer: continue from its float values
-        e = launch_seed_accum(out_sums, slot->acc, slot->flags, npx, st);
+        e = launch_seed_accum(out_sums, acc, flags, npx, st);
     } else {
         // state for this address: kept where out_sums still holds what it last
         // finalized to, restarted from the floats elsewhere (a reallocated buffer)
-        e = launch_reconcile_accum(out_sums, slot->acc, slot->flags, npx, st);
+        e = launch_reconcile_accum(out_sums, acc, flags, npx, st);
     }
     if (e == hipSuccess && P.spp > 0)
         e = c->diag_buf ? launch_render_f32_diag(P, plan.lds_bytes, st, plan.trav, plan.block, plan.wpe)
                         : launch_render_f32(P, plan.lds_bytes, st, plan.block, plan.wpe, plan.trav);
-    if (e == hipSuccess) e = launch_finalize(slot->acc, slot->accp, slot->flags, out_sums, npx, st);
-    return launch_rc(c, e);
+    if (e == hipSuccess) e = launch_finalize(acc, accp, flags, out_sums, npx, st);
+    return RT_OK;
 }
 
 // fp64 on persistent lanes (TRAV_PERSIST): every sample's radiance goes to d_samples, then
 // the ordered reduction; passes bound the buffer to sample_buffer_mb (a shard with no tiles
 // has nothing to store: npx = 0)
-static int render_range_f64(rt_ctx* c, const LaunchPlan& plan, const RenderParams& P, size_t npx, hipStream_t st) {
+static int render_range_f64(rt_ctx* c, const LaunchPlan& plan, const RenderParams& P, size_t npx, hipStream_t st,
+                            hipError_t& e) {
     const int spp = P.spp;
     const size_t eb = elem_bytes(c);
     int rc;
@@ -746,32 +705,31 @@ static int render_range_f64(rt_ctx* c, const LaunchPlan& plan, const RenderParam
     const size_t fit = std::min(MAX_PASS_SAMPLES, npx > 0 ? ((size_t)c->tuning.sample_buffer_mb << 20) /
                                                                 (npx * 3 * eb) : (size_t)spp);
     const int pass_spp = std::max(1, (size_t)spp < fit ? spp : (int)std::max<size_t>(1, fit));
-    if ((rc = grow(c, &c->d_samples, &c->samples_cap, npx * 3 * eb * (size_t)std::max(1, pass_spp)))) return rc;
-    if (!c->d_queue64) HIPCHK(c, hipMalloc((void**)&c->d_queue64, QUEUE_CTRL_BYTES));
-    const double balance = c->n_mnodes > 0 ? c->tuning.mesh_item_balance : c->tuning.item_balance;
-    hipError_t e = hipSuccess;
+    if ((rc = reserve(c, c->d_samples, npx * 3 * eb * (size_t)std::max(1, pass_spp)))) return rc;
+    HIPCHK(c, c->d_queue64.reserve(QUEUE_CTRL_BYTES));
+    const double balance = c->scene.n_mnodes > 0 ? c->tuning.mesh_item_balance : c->tuning.item_balance;
     if (P.out_segs && !P.accumulate) e = hipMemsetAsync(P.out_segs, 0, npx * sizeof(uint32_t), st);
     if (e == hipSuccess && spp == 0 && !P.accumulate) e = hipMemsetAsync(P.out_sums, 0, npx * 3 * eb, st);
     for (int done = 0; done < spp && npx > 0 && e == hipSuccess; done += pass_spp) {
         RenderParams Q = P;
-        Q.queue = c->d_queue64;
+        Q.queue = c->d_queue64.as<uint32_t>();
         Q.sample_begin = P.sample_begin + done;
         Q.spp = spp - done < pass_spp ? spp - done : pass_spp;
-        Q.samples = c->d_samples;
+        Q.samples = c->d_samples.p;
         const double lanes = (double)Q.max_wgs * plan.block;
         plan_phases(Q, Q.spp, lanes, (double)npx, balance, item_cap(c, plan.trav, lanes, (double)npx));
-        e = hipMemsetAsync(c->d_queue64, 0, QUEUE_CTRL_BYTES, st);
+        e = hipMemsetAsync(Q.queue, 0, QUEUE_CTRL_BYTES, st);
         if (e == hipSuccess) e = launch_render_f64(Q, plan.lds_bytes, st, plan.f64_kernel);
         if (e == hipSuccess)
-            e = launch_reduce(c->d_samples, P.out_sums, (int)eb, npx * 3, Q.spp, (P.accumulate || done > 0) ? 1 : 0, st);
+            e = launch_reduce(c->d_samples.p, P.out_sums, (int)eb, npx * 3, Q.spp, (P.accumulate || done > 0) ? 1 : 0, st);
     }
-    return launch_rc(c, e);
+    return RT_OK;
 }
 
 int rt_render_range(rt_ctx* c, const rt_camera* cam, int sample_begin, int spp, int max_depth, int shard,
                     int num_shards, int accumulate, void* out_sums, uint32_t* out_segments, void* stream) {
     if (!c) return RT_ERR_INVALID;
-    if (!c->has_scene) return fail(c, RT_ERR_NO_SCENE, "rt_render before rt_upload_scene");
+    if (!c->scene.has_scene) return fail(c, RT_ERR_NO_SCENE, "rt_render before rt_upload_scene");
     int rc = check_camera(c, cam);
     if (rc) return rc;
     if (spp < 0 || sample_begin < 0) return fail(c, RT_ERR_INVALID, "samples [%d, +%d)", sample_begin, spp);
@@ -782,7 +740,7 @@ int rt_render_range(rt_ctx* c, const rt_camera* cam, int sample_begin, int spp, 
     if (rt_shard_layout(cam->image_width, cam->image_height, shard, num_shards, &si) != RT_OK)
         return fail(c, RT_ERR_INVALID, "bad shard %d of %d", shard, num_shards);
     HIPCHK(c, hipSetDevice(c->device));
-    const bool f32 = c->precision == RT_PREC_F32, mesh = c->n_mnodes > 0;
+    const bool f32 = c->precision == RT_PREC_F32, mesh = c->scene.n_mnodes > 0;
     const LaunchPlan plan = plan_launch(c, grid_in_reach(c, cam));
     if (plan.lds_bytes > 160 * 1024)
         return fail(c, RT_ERR_LIMIT, "render needs %zu B of LDS per workgroup", plan.lds_bytes);
@@ -818,23 +776,22 @@ int rt_render_range(rt_ctx* c, const rt_camera* cam, int sample_begin, int spp, 
     P.max_wgs = std::max(1, plan.wgs_per_cu * (c->n_cu > 0 ? c->n_cu : 256));
     if (c->tuning.grid_workgroups > 0) P.max_wgs = c->tuning.grid_workgroups;
     apply_grid(c, plan.trav, P);
-    hipStream_t st = stream ? (hipStream_t)stream : c->stream;
+    hipStream_t st = stream_of(c, stream);
     const size_t npx = (size_t)si.shard_tiles * 64;
     HIPCHK(c, hipEventRecord(c->ev0, st));
     // fp32: packed per-launch sums hold <= FIX_LAUNCH_SAMPLES samples: consecutive ranges,
     // timed as one (rt_last_kernel_ms spans all of them)
     const int range = f32 ? FIX_LAUNCH_SAMPLES : std::max(1, spp);
     int done = 0;
+    hipError_t e = hipSuccess;
     do {
         P.sample_begin = sample_begin + done;
         P.spp = std::min(spp - done, range);
         P.accumulate = accumulate || done > 0 ? 1 : 0;
-        if ((rc = f32 ? render_range_f32(c, plan, P, npx, st) : render_range_f64(c, plan, P, npx, st))) return rc;
+        if ((rc = f32 ? render_range_f32(c, plan, P, npx, st, e) : render_range_f64(c, plan, P, npx, st, e))) return rc;
         done += range;
-    } while (done < spp);
-    HIPCHK(c, hipEventRecord(c->ev1, st));
-    c->timed = true;
-    return RT_OK;
+    } while (done < spp && e == hipSuccess);
+    return timed_end(c, st, e, "render launch");
 }
 
 int rt_render(rt_ctx* c, const rt_camera* cam, int spp, int max_depth, int shard, int num_shards, void* out_sums,
@@ -854,7 +811,7 @@ int rt_unshard(rt_ctx* c, const void* gathered, int width, int height, int num_s
     if (!c || !gathered || !frame || width <= 0 || height <= 0 || num_shards <= 0) return RT_ERR_INVALID;
     rt_shard_info si;
     rt_shard_layout(width, height, 0, num_shards, &si);
-    hipStream_t st = stream ? (hipStream_t)stream : c->stream;
+    hipStream_t st = stream_of(c, stream);
     HIPCHK(c, hipSetDevice(c->device));
     HIPCHK(c, launch_unshard(gathered, frame, (int)elem_bytes(c), 3, width, height, si.tiles_x, num_shards,
                              si.max_shard_tiles, st));
@@ -863,7 +820,7 @@ int rt_unshard(rt_ctx* c, const void* gathered, int width, int height, int num_s
 
 int rt_quantize(rt_ctx* c, const void* frame, int width, int height, int spp, int32_t* rgb, void* stream) {
     if (!c || !frame || !rgb || width <= 0 || height <= 0) return RT_ERR_INVALID;
-    hipStream_t st = stream ? (hipStream_t)stream : c->stream;
+    hipStream_t st = stream_of(c, stream);
     HIPCHK(c, hipSetDevice(c->device));
     HIPCHK(c, launch_quantize(frame, (int)elem_bytes(c), rgb, (size_t)width * height * 3, spp, st));
     return RT_OK;
@@ -879,22 +836,22 @@ int rt_render_frame(rt_ctx* c, const rt_camera* cam, int spp, int max_depth, voi
     rt_shard_info si;
     rt_shard_layout(W, H, 0, 1, &si);
     const size_t npx_tiles = (size_t)si.num_tiles * 64, npx = (size_t)W * H, eb = elem_bytes(c);
-    if ((rc = grow(c, &c->d_shard, &c->shard_cap, npx_tiles * 3 * eb))) return rc;
-    if ((rc = grow(c, &c->d_frame, &c->frame_cap, npx * 3 * eb))) return rc;
-    if ((rc = grow(c, (void**)&c->d_segs, &c->segs_cap, npx_tiles * 4))) return rc;
-    if ((rc = grow(c, (void**)&c->d_segs_frame, &c->segs_frame_cap, npx * 4))) return rc;
-    if ((rc = grow(c, (void**)&c->d_rgb, &c->rgb_cap, npx * 3 * 4))) return rc;
-    if ((rc = rt_render(c, cam, spp, max_depth, 0, 1, c->d_shard, c->d_segs, nullptr))) return rc;
-    HIPCHK(c, launch_unshard(c->d_shard, c->d_frame, (int)eb, 3, W, H, si.tiles_x, 1, si.max_shard_tiles, c->stream));
+    if ((rc = reserve(c, c->d_shard, npx_tiles * 3 * eb))) return rc;
+    if ((rc = reserve(c, c->d_frame, npx * 3 * eb))) return rc;
+    if ((rc = reserve(c, c->d_segs, npx_tiles * 4))) return rc;
+    if ((rc = reserve(c, c->d_segs_frame, npx * 4))) return rc;
+    if ((rc = reserve(c, c->d_rgb, npx * 3 * 4))) return rc;
+    if ((rc = rt_render(c, cam, spp, max_depth, 0, 1, c->d_shard.p, c->d_segs.as<uint32_t>(), nullptr))) return rc;
+    HIPCHK(c, launch_unshard(c->d_shard.p, c->d_frame.p, (int)eb, 3, W, H, si.tiles_x, 1, si.max_shard_tiles, c->stream));
     if (segments_host)
-        HIPCHK(c, launch_unshard(c->d_segs, c->d_segs_frame, 4, 1, W, H, si.tiles_x, 1, si.max_shard_tiles,
+        HIPCHK(c, launch_unshard(c->d_segs.p, c->d_segs_frame.p, 4, 1, W, H, si.tiles_x, 1, si.max_shard_tiles,
                                  c->stream));
-    if (rgb_host) HIPCHK(c, launch_quantize(c->d_frame, (int)eb, c->d_rgb, npx * 3, spp, c->stream));
+    if (rgb_host) HIPCHK(c, launch_quantize(c->d_frame.p, (int)eb, c->d_rgb.as<int32_t>(), npx * 3, spp, c->stream));
     if (sums_host)
-        HIPCHK(c, hipMemcpyAsync(sums_host, c->d_frame, npx * 3 * eb, hipMemcpyDeviceToHost, c->stream));
-    if (rgb_host) HIPCHK(c, hipMemcpyAsync(rgb_host, c->d_rgb, npx * 3 * 4, hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(c, hipMemcpyAsync(sums_host, c->d_frame.p, npx * 3 * eb, hipMemcpyDeviceToHost, c->stream));
+    if (rgb_host) HIPCHK(c, hipMemcpyAsync(rgb_host, c->d_rgb.p, npx * 3 * 4, hipMemcpyDeviceToHost, c->stream));
     if (segments_host)
-        HIPCHK(c, hipMemcpyAsync(segments_host, c->d_segs_frame, npx * 4, hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(c, hipMemcpyAsync(segments_host, c->d_segs_frame.p, npx * 4, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
     return RT_OK;
 }
@@ -906,7 +863,7 @@ int rt_finish_frame_u8(rt_ctx* c, const void* gathered, int width, int height, i
         return fail(c, RT_ERR_INVALID, "finish %dx%d over %d shards at %d spp", width, height, num_shards, spp);
     rt_shard_info si;
     rt_shard_layout(width, height, 0, num_shards, &si);
-    hipStream_t st = stream ? (hipStream_t)stream : c->stream;
+    hipStream_t st = stream_of(c, stream);
     HIPCHK(c, hipSetDevice(c->device));
     HIPCHK(c, launch_finish_u8(gathered, (int)elem_bytes(c), rgb8, width, height, si.tiles_x, num_shards,
                                si.max_shard_tiles, spp, st));
@@ -933,8 +890,8 @@ int rt_render_frame_u8(rt_ctx* c, const rt_camera* cam, int spp, int max_depth, 
     rt_shard_info si;
     rt_shard_layout(W, H, 0, 1, &si);
     const size_t bytes = (size_t)W * H * 3;
-    if ((rc = grow(c, &c->d_shard, &c->shard_cap, (size_t)si.num_tiles * 64 * 3 * elem_bytes(c)))) return rc;
-    if ((rc = grow(c, (void**)&c->d_rgb8, &c->rgb8_cap, bytes))) return rc;
+    if ((rc = reserve(c, c->d_shard, (size_t)si.num_tiles * 64 * 3 * elem_bytes(c)))) return rc;
+    if ((rc = reserve(c, c->d_rgb8, bytes))) return rc;
     // copy straight into page-locked caller memory, else through the context's staging buffer
     hipPointerAttribute_t attr;
     bool pinned = hipPointerGetAttributes(&attr, rgb8_host) == hipSuccess && attr.type == hipMemoryTypeHost;
@@ -946,10 +903,10 @@ int rt_render_frame_u8(rt_ctx* c, const rt_camera* cam, int spp, int max_depth, 
         HIPCHK(c, hipHostMalloc(&c->h_pinned, bytes, hipHostMallocDefault));
         c->pinned_cap = bytes;
     }
-    if ((rc = rt_render(c, cam, spp, max_depth, 0, 1, c->d_shard, nullptr, nullptr))) return rc;
-    HIPCHK(c, launch_finish_u8(c->d_shard, (int)elem_bytes(c), c->d_rgb8, W, H, si.tiles_x, 1, si.max_shard_tiles, spp,
-                               c->stream));
-    HIPCHK(c, hipMemcpyAsync(pinned ? (void*)rgb8_host : c->h_pinned, c->d_rgb8, bytes, hipMemcpyDeviceToHost,
+    if ((rc = rt_render(c, cam, spp, max_depth, 0, 1, c->d_shard.p, nullptr, nullptr))) return rc;
+    HIPCHK(c, launch_finish_u8(c->d_shard.p, (int)elem_bytes(c), c->d_rgb8.as<uint8_t>(), W, H, si.tiles_x, 1,
+                               si.max_shard_tiles, spp, c->stream));
+    HIPCHK(c, hipMemcpyAsync(pinned ? (void*)rgb8_host : c->h_pinned, c->d_rgb8.p, bytes, hipMemcpyDeviceToHost,
                              c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
     if (!pinned) std::memcpy(rgb8_host, c->h_pinned, bytes);
@@ -978,8 +935,8 @@ int rt_render_frame_multi(rt_ctx** cs, int n, const rt_camera* cam, int spp, int
     for (int r = 0; r < n; ++r) {
         rt_ctx* c = cs[r];
         HIPCHK(c0, hipSetDevice(c->device));
-        if ((rc = grow(c, &c->d_shard, &c->shard_cap, per))) return rc;
-        if ((rc = rt_render(c, cam, spp, max_depth, r, n, c->d_shard, nullptr, nullptr)) != RT_OK) {
+        if ((rc = reserve(c, c->d_shard, per))) return rc;
+        if ((rc = rt_render(c, cam, spp, max_depth, r, n, c->d_shard.p, nullptr, nullptr)) != RT_OK) {
             if (c != c0) c0->err = std::string("context ") + std::to_string(r) + ": " + c->err;
             return rc;
         }
@@ -997,28 +954,28 @@ int rt_render_frame_multi(rt_ctx** cs, int n, const rt_camera* cam, int spp, int
             (void)hipGetLastError();
         }
     }
-    if ((rc = grow(c0, &c0->d_gather, &c0->gather_cap, per * (size_t)n))) return rc;
-    if ((rc = grow(c0, &c0->d_frame, &c0->frame_cap, npx * 3 * eb))) return rc;
-    if ((rc = grow(c0, (void**)&c0->d_rgb, &c0->rgb_cap, npx * 3 * 4))) return rc;
+    if ((rc = reserve(c0, c0->d_gather, per * (size_t)n))) return rc;
+    if ((rc = reserve(c0, c0->d_frame, npx * 3 * eb))) return rc;
+    if ((rc = reserve(c0, c0->d_rgb, npx * 3 * 4))) return rc;
     if (c0->comm) {
         // RCCL: one grouped ncclGather, rank r on context r's stream after its render
-        if ((rc = rt_comm_gather_group(cs, n, per / eb, c0->d_gather))) return rc;
+        if ((rc = rt_comm_gather_group(cs, n, per / eb, c0->d_gather.p))) return rc;
     } else {
         for (int r = 0; r < n; ++r) {
             rt_ctx* c = cs[r];
             HIPCHK(c0, hipStreamWaitEvent(c0->stream, c->ev1, 0));   // ev1: end of that context's render
-            void* dst = (char*)c0->d_gather + (size_t)r * per;
+            void* dst = (char*)c0->d_gather.p + (size_t)r * per;
             if (c->device == c0->device)
-                HIPCHK(c0, hipMemcpyAsync(dst, c->d_shard, per, hipMemcpyDeviceToDevice, c0->stream));
+                HIPCHK(c0, hipMemcpyAsync(dst, c->d_shard.p, per, hipMemcpyDeviceToDevice, c0->stream));
             else
-                HIPCHK(c0, hipMemcpyPeerAsync(dst, c0->device, c->d_shard, c->device, per, c0->stream));
+                HIPCHK(c0, hipMemcpyPeerAsync(dst, c0->device, c->d_shard.p, c->device, per, c0->stream));
         }
     }
-    HIPCHK(c0, launch_unshard(c0->d_gather, c0->d_frame, (int)eb, 3, W, H, si.tiles_x, n, si.max_shard_tiles,
+    HIPCHK(c0, launch_unshard(c0->d_gather.p, c0->d_frame.p, (int)eb, 3, W, H, si.tiles_x, n, si.max_shard_tiles,
                               c0->stream));
-    if (rgb_host) HIPCHK(c0, launch_quantize(c0->d_frame, (int)eb, c0->d_rgb, npx * 3, spp, c0->stream));
-    if (sums_host) HIPCHK(c0, hipMemcpyAsync(sums_host, c0->d_frame, npx * 3 * eb, hipMemcpyDeviceToHost, c0->stream));
-    if (rgb_host) HIPCHK(c0, hipMemcpyAsync(rgb_host, c0->d_rgb, npx * 3 * 4, hipMemcpyDeviceToHost, c0->stream));
+    if (rgb_host) HIPCHK(c0, launch_quantize(c0->d_frame.p, (int)eb, c0->d_rgb.as<int32_t>(), npx * 3, spp, c0->stream));
+    if (sums_host) HIPCHK(c0, hipMemcpyAsync(sums_host, c0->d_frame.p, npx * 3 * eb, hipMemcpyDeviceToHost, c0->stream));
+    if (rgb_host) HIPCHK(c0, hipMemcpyAsync(rgb_host, c0->d_rgb.p, npx * 3 * 4, hipMemcpyDeviceToHost, c0->stream));
     HIPCHK(c0, hipStreamSynchronize(c0->stream));
     return RT_OK;
 }
@@ -1031,7 +988,7 @@ static int query_setup(rt_ctx* c, const char* what, RenderParams& P, size_t& lds
     rt_camera cam{};
     cam.image_width = cam.image_height = 1;
     fill_params(c, view ? view : &cam, 1, 1, plan_launch(c, true).mesh_stack, P);
-    P.nodes = c->d_nodes;   // (the time-binned copies are a render-kernel option)
+    P.nodes = c->scene.d_nodes.as<Node>();   // (the time-binned copies are a render-kernel option)
     lds = lds_scene_bytes_at(c, TRACE_BLOCK) + (size_t)TRACE_BLOCK * (size_t)P.mstack * 4;
     if (lds > 160 * 1024) return fail(c, RT_ERR_LIMIT, "%s needs %zu B of LDS per workgroup", what, lds);
     return RT_OK;
@@ -1040,22 +997,20 @@ static int query_setup(rt_ctx* c, const char* what, RenderParams& P, size_t& lds
 static int trace_rays(rt_ctx* c, const void* rays, int n, const int32_t* origin_ids, rt_hit* hits, void* stream,
                       unsigned long long* diag) {
     if (!c) return RT_ERR_INVALID;
-    if (!c->has_scene) return fail(c, RT_ERR_NO_SCENE, "rt_trace_rays before rt_upload_scene");
+    if (!c->scene.has_scene) return fail(c, RT_ERR_NO_SCENE, "rt_trace_rays before rt_upload_scene");
     if (n < 0 || (n > 0 && (!rays || !hits))) return fail(c, RT_ERR_INVALID, "rt_trace_rays: %d rays, rays %p, hits %p", n, rays, hits);
     RenderParams P;
     size_t lds;
     if (int rc = query_setup(c, "rt_trace_rays", P, lds)) return rc;
     P.diag = diag;
-    hipStream_t st = stream ? (hipStream_t)stream : c->stream;
+    const int *remap = c->scene.d_remap.as<int>(), *unmap = c->scene.d_unmap.as<int>();
+    hipStream_t st = stream_of(c, stream);
     HIPCHK(c, hipEventRecord(c->ev0, st));
     const hipError_t e =
         c->precision == RT_PREC_F64
-            ? launch_trace_f64(P, lds, st, rays, n, hits, c->d_remap, origin_ids, c->d_unmap, c->n_unmap)
-            : launch_trace_f32(P, lds, st, rays, n, hits, c->d_remap, origin_ids, c->d_unmap, c->n_unmap, diag != nullptr);
-    if (e != hipSuccess) return fail(c, RT_ERR_HIP, "trace launch: %s", hipGetErrorString(e));
-    HIPCHK(c, hipEventRecord(c->ev1, st));
-    c->timed = true;
-    return RT_OK;
+            ? launch_trace_f64(P, lds, st, rays, n, hits, remap, origin_ids, unmap, c->scene.n_unmap)
+            : launch_trace_f32(P, lds, st, rays, n, hits, remap, origin_ids, unmap, c->scene.n_unmap, diag != nullptr);
+    return timed_end(c, st, e, "trace launch");
 }
 
 int rt_trace_rays(rt_ctx* c, const void* rays, int n, rt_hit* hits, void* stream) {
@@ -1068,26 +1023,23 @@ int rt_trace_rays_from(rt_ctx* c, const void* rays, int n, const int32_t* origin
 
 int rt_occluded(rt_ctx* c, const void* rays, int n, const void* intervals, uint8_t* occluded, void* stream) {
     if (!c) return RT_ERR_INVALID;
-    if (!c->has_scene) return fail(c, RT_ERR_NO_SCENE, "rt_occluded before rt_upload_scene");
+    if (!c->scene.has_scene) return fail(c, RT_ERR_NO_SCENE, "rt_occluded before rt_upload_scene");
     if (n < 0 || (n > 0 && (!rays || !occluded)))
         return fail(c, RT_ERR_INVALID, "rt_occluded: %d rays, rays %p, occluded %p", n, rays, (void*)occluded);
     RenderParams P;
     size_t lds;
     if (int rc = query_setup(c, "rt_occluded", P, lds)) return rc;
-    hipStream_t st = stream ? (hipStream_t)stream : c->stream;
+    hipStream_t st = stream_of(c, stream);
     HIPCHK(c, hipEventRecord(c->ev0, st));
     const hipError_t e = c->precision == RT_PREC_F64 ? launch_occluded_f64(P, lds, st, rays, n, intervals, occluded)
                                                      : launch_occluded_f32(P, lds, st, rays, n, intervals, occluded);
-    if (e != hipSuccess) return fail(c, RT_ERR_HIP, "occlusion launch: %s", hipGetErrorString(e));
-    HIPCHK(c, hipEventRecord(c->ev1, st));
-    c->timed = true;
-    return RT_OK;
+    return timed_end(c, st, e, "occlusion launch");
 }
 
 int rt_radiance_rays(rt_ctx* c, const void* rays, int n, const rt_path_key* keys, int max_depth, void* radiance,
                      uint32_t* segments, void* stream) {
     if (!c) return RT_ERR_INVALID;
-    if (!c->has_scene) return fail(c, RT_ERR_NO_SCENE, "rt_radiance_rays before rt_upload_scene");
+    if (!c->scene.has_scene) return fail(c, RT_ERR_NO_SCENE, "rt_radiance_rays before rt_upload_scene");
     if (n < 0 || (n > 0 && (!rays || !radiance)))
         return fail(c, RT_ERR_INVALID, "rt_radiance_rays: %d rays, rays %p, radiance %p", n, rays, radiance);
     if (c->precision == RT_PREC_F64 && max_depth > 64)
@@ -1097,25 +1049,22 @@ int rt_radiance_rays(rt_ctx* c, const void* rays, int n, const rt_path_key* keys
     if (int rc = query_setup(c, "rt_radiance_rays", P, lds)) return rc;
     if (n == 0) return RT_OK;
     P.max_depth = max_depth;
-    if (!c->d_queue_rad) HIPCHK(c, hipMalloc((void**)&c->d_queue_rad, QUEUE_CTRL_BYTES));
-    P.queue = c->d_queue_rad;
-    hipStream_t st = stream ? (hipStream_t)stream : c->stream;
+    HIPCHK(c, c->d_queue_rad.reserve(QUEUE_CTRL_BYTES));
+    P.queue = c->d_queue_rad.as<uint32_t>();
+    hipStream_t st = stream_of(c, stream);
     HIPCHK(c, hipEventRecord(c->ev0, st));
     hipError_t e;
     if (max_depth <= 0) {   // camera_cpu.h:9-10: no path, no light (all-zero bits are 0 in either precision)
         e = hipMemsetAsync(radiance, 0, (size_t)n * 3 * elem_bytes(c), st);
         if (e == hipSuccess && segments) e = hipMemsetAsync(segments, 0, (size_t)n * sizeof(uint32_t), st);
     } else {
-        e = hipMemsetAsync(c->d_queue_rad, 0, QUEUE_CTRL_BYTES, st);
+        e = hipMemsetAsync(P.queue, 0, QUEUE_CTRL_BYTES, st);
         if (e == hipSuccess)
             e = c->precision == RT_PREC_F64
                     ? launch_radiance_f64(P, lds, st, rays, n, keys, radiance, segments, c->n_cu)
                     : launch_radiance_f32(P, lds, st, rays, n, keys, radiance, segments, c->n_cu);
     }
-    if (e != hipSuccess) return fail(c, RT_ERR_HIP, "radiance launch: %s", hipGetErrorString(e));
-    HIPCHK(c, hipEventRecord(c->ev1, st));
-    c->timed = true;
-    return RT_OK;
+    return timed_end(c, st, e, "radiance launch");
 }
 
 // rt_render_pixels / rt_camera_rays: offsets = the exclusive scan of the valid jobs' counts on
@@ -1124,14 +1073,15 @@ int rt_radiance_rays(rt_ctx* c, const void* rays, int n, const rt_path_key* keys
 static int pixel_scan(rt_ctx* c, const char* what, const rt_camera* cam, const rt_pixel_job* jobs, int num_jobs,
                       hipStream_t st, unsigned long long& total) {
     int rc;
-    if ((rc = grow(c, (void**)&c->d_px_offsets, &c->px_offsets_cap, ((size_t)num_jobs + 1) * sizeof(unsigned long long))))
+    if ((rc = reserve(c, c->d_px_offsets, ((size_t)num_jobs + 1) * sizeof(unsigned long long))))
         return rc;
     const uint32_t npix = (uint32_t)((long long)cam->image_width * cam->image_height);   // (check_camera: < 2^29)
     size_t tmp = 0;
-    HIPCHK(c, launch_pixel_scan(jobs, num_jobs, npix, c->d_px_offsets, nullptr, &tmp, st));
-    if ((rc = grow(c, &c->d_px_scan, &c->px_scan_cap, tmp))) return rc;
-    HIPCHK(c, launch_pixel_scan(jobs, num_jobs, npix, c->d_px_offsets, c->d_px_scan, &tmp, st));
-    HIPCHK(c, hipMemcpyAsync(&total, c->d_px_offsets + num_jobs, sizeof(total), hipMemcpyDeviceToHost, st));
+    unsigned long long* off = c->d_px_offsets.as<unsigned long long>();
+    HIPCHK(c, launch_pixel_scan(jobs, num_jobs, npix, off, nullptr, &tmp, st));
+    if ((rc = reserve(c, c->d_px_scan, tmp))) return rc;
+    HIPCHK(c, launch_pixel_scan(jobs, num_jobs, npix, off, c->d_px_scan.p, &tmp, st));
+    HIPCHK(c, hipMemcpyAsync(&total, off + num_jobs, sizeof(total), hipMemcpyDeviceToHost, st));
     HIPCHK(c, hipStreamSynchronize(st));
     if (total > 0x7fffffffull) return fail(c, RT_ERR_LIMIT, "%s: %llu samples (> 2^31 - 1)", what, total);
     return RT_OK;
@@ -1150,7 +1100,7 @@ int rt_camera_rays(rt_ctx* c, const rt_camera* cam, const rt_pixel_job* jobs, in
         return RT_OK;
     }
     HIPCHK(c, hipSetDevice(c->device));
-    hipStream_t st = stream ? (hipStream_t)stream : c->stream;
+    hipStream_t st = stream_of(c, stream);
     HIPCHK(c, hipEventRecord(c->ev0, st));
     unsigned long long total = 0;
     rc = pixel_scan(c, "rt_camera_rays", cam, jobs, num_jobs, st, total);
@@ -1161,14 +1111,12 @@ int rt_camera_rays(rt_ctx* c, const rt_camera* cam, const rt_pixel_job* jobs, in
     RenderParams P;
     std::memset(&P, 0, sizeof(P));
     fill_camera(c, cam, P);
+    const unsigned long long* off = c->d_px_offsets.as<unsigned long long>();
     const hipError_t e =
         c->precision == RT_PREC_F64
-            ? launch_camera_rays_f64(P, st, jobs, c->d_px_offsets, num_jobs, (long long)total, rays, keys, ray_job)
-            : launch_camera_rays_f32(P, st, jobs, c->d_px_offsets, num_jobs, (long long)total, rays, keys, ray_job);
-    if (e != hipSuccess) return fail(c, RT_ERR_HIP, "camera-ray launch: %s", hipGetErrorString(e));
-    HIPCHK(c, hipEventRecord(c->ev1, st));
-    c->timed = true;
-    return RT_OK;
+            ? launch_camera_rays_f64(P, st, jobs, off, num_jobs, (long long)total, rays, keys, ray_job)
+            : launch_camera_rays_f32(P, st, jobs, off, num_jobs, (long long)total, rays, keys, ray_job);
+    return timed_end(c, st, e, "camera-ray launch");
 }
 
 // What a job-list query (rt_render_pixels, rt_render_pixels_moments, rt_render_pixels_aov) holds
@@ -1187,20 +1135,20 @@ struct JobQuery {
 static int job_query_begin(rt_ctx* c, const char* what, const rt_camera* cam, const rt_pixel_job* jobs, int num_jobs,
                            void* stream, bool scan, const std::function<int()>& args, JobQuery& q) {
     if (!c) return RT_ERR_INVALID;
-    if (!c->has_scene) return fail(c, RT_ERR_NO_SCENE, "%s before rt_upload_scene", what);
+    if (!c->scene.has_scene) return fail(c, RT_ERR_NO_SCENE, "%s before rt_upload_scene", what);
     int rc = check_camera(c, cam);
     if (rc) return rc;
     if ((rc = args())) return rc;
     if ((rc = query_setup(c, what, q.P, q.lds, cam))) return rc;
     q.total = 0;
     if (num_jobs == 0) return RT_OK;
-    q.st = stream ? (hipStream_t)stream : c->stream;
+    q.st = stream_of(c, stream);
     HIPCHK(c, hipEventRecord(c->ev0, q.st));
     return scan ? pixel_scan(c, what, cam, jobs, num_jobs, q.st, q.total) : RT_OK;
 }
 
 // The fp64 passes of those calls: a sample's record is doubles and one 32-bit word, sample_bytes
-// in all, kept in two arrays (c->d_px_samples, c->d_px_sseg) that hold a pass -- at most
+// in all, kept in two arrays (c->d_px_samples.as<double>(), c->d_px_sseg.as<uint32_t>()) that hold a pass -- at most
 // floor(sample_buffer_mb 2^20 / sample_bytes) samples.  run(q0, q1) launches and reduces flat
 // samples [q0, q1), in order; the first pass also fills the jobs without samples, so it runs even
 // when T = 0.  e: the first launch error.
@@ -1209,9 +1157,9 @@ static int sample_passes(rt_ctx* c, unsigned long long total, size_t sample_byte
     const unsigned long long fit = ((unsigned long long)c->tuning.sample_buffer_mb << 20) / sample_bytes;
     const unsigned long long pass = std::max(1ull, std::min(fit, total));
     int rc;
-    if ((rc = grow(c, (void**)&c->d_px_samples, &c->px_samples_cap, (size_t)pass * (sample_bytes - sizeof(uint32_t)))))
+    if ((rc = reserve(c, c->d_px_samples, (size_t)pass * (sample_bytes - sizeof(uint32_t)))))
         return rc;
-    if ((rc = grow(c, (void**)&c->d_px_sseg, &c->px_sseg_cap, (size_t)pass * sizeof(uint32_t)))) return rc;
+    if ((rc = reserve(c, c->d_px_sseg, (size_t)pass * sizeof(uint32_t)))) return rc;
     unsigned long long q0 = 0;
     do {
         const unsigned long long q1 = std::min(total, q0 + pass);
@@ -1251,53 +1199,52 @@ static int render_pixels(rt_ctx* c, const char* what, const rt_camera* cam, cons
         }
     } else {
         P.max_depth = max_depth;
-        if (!c->d_queue_px) HIPCHK(c, hipMalloc((void**)&c->d_queue_px, QUEUE_CTRL_BYTES));
-        P.queue = c->d_queue_px;
-        const unsigned long long* off = c->d_px_offsets;
+        HIPCHK(c, c->d_queue_px.reserve(QUEUE_CTRL_BYTES));
+        P.queue = c->d_queue_px.as<uint32_t>();
+        const unsigned long long* off = c->d_px_offsets.as<unsigned long long>();
         if (c->precision != RT_PREC_F64) {
-            if ((rc = grow(c, (void**)&c->d_px_acc, &c->px_acc_cap, nj * 3 * sizeof(long long)))) return rc;
-            if ((rc = grow(c, (void**)&c->d_px_flags, &c->px_flags_cap, nj * sizeof(uint32_t)))) return rc;
+            if ((rc = reserve(c, c->d_px_acc, nj * 3 * sizeof(long long)))) return rc;
+            if ((rc = reserve(c, c->d_px_flags, nj * sizeof(uint32_t)))) return rc;
             if (moments) {
-                if ((rc = grow(c, (void**)&c->d_px_sq, &c->px_sq_cap, nj * 6 * sizeof(unsigned long long)))) return rc;
-                if ((rc = grow(c, (void**)&c->d_px_sqflags, &c->px_sqflags_cap, nj * sizeof(uint32_t)))) return rc;
+                if ((rc = reserve(c, c->d_px_sq, nj * 6 * sizeof(unsigned long long)))) return rc;
+                if ((rc = reserve(c, c->d_px_sqflags, nj * sizeof(uint32_t)))) return rc;
             }
-            e = launch_pixels_seed(off, num_jobs, acc, (const float*)out_sums, c->d_px_acc, c->d_px_flags, out_segments,
-                                   st);
+            long long* sum = c->d_px_acc.as<long long>();
+            uint32_t* flags = c->d_px_flags.as<uint32_t>();
+            unsigned long long* sq = c->d_px_sq.as<unsigned long long>();
+            uint32_t* sqflags = c->d_px_sqflags.as<uint32_t>();
+            e = launch_pixels_seed(off, num_jobs, acc, (const float*)out_sums, sum, flags, out_segments, st);
             if (e == hipSuccess && moments)
-                e = launch_pixels_seed_moments(off, num_jobs, acc, (const float*)out_sumsq, c->d_px_sq, c->d_px_sqflags,
-                                               st);
-            if (e == hipSuccess) e = hipMemsetAsync(c->d_queue_px, 0, QUEUE_CTRL_BYTES, st);
+                e = launch_pixels_seed_moments(off, num_jobs, acc, (const float*)out_sumsq, sq, sqflags, st);
+            if (e == hipSuccess) e = hipMemsetAsync(P.queue, 0, QUEUE_CTRL_BYTES, st);
             if (e == hipSuccess)
                 e = moments ? launch_pixels_moments_f32(P, lds, st, jobs, off, num_jobs, total, 0, (int)total,
-                                                        (unsigned long long*)c->d_px_acc, c->d_px_flags, out_segments,
-                                                        c->d_px_sq, c->d_px_sqflags, c->n_cu, c->tuning.grid_workgroups)
+                                                        (unsigned long long*)sum, flags, out_segments, sq, sqflags,
+                                                        c->n_cu, c->tuning.grid_workgroups)
                             : launch_pixels_f32(P, lds, st, jobs, off, num_jobs, total, 0, (int)total,
-                                                (unsigned long long*)c->d_px_acc, c->d_px_flags, out_segments, c->n_cu);
-            if (e == hipSuccess)
-                e = launch_pixels_finalize(off, num_jobs, acc, c->d_px_acc, c->d_px_flags, (float*)out_sums, st);
+                                                (unsigned long long*)sum, flags, out_segments, c->n_cu);
+            if (e == hipSuccess) e = launch_pixels_finalize(off, num_jobs, acc, sum, flags, (float*)out_sums, st);
             if (e == hipSuccess && moments)
-                e = launch_pixels_finalize_moments(off, num_jobs, acc, c->d_px_sq, c->d_px_sqflags, (float*)out_sumsq,
-                                                   st);
+                e = launch_pixels_finalize_moments(off, num_jobs, acc, sq, sqflags, (float*)out_sumsq, st);
         } else {
             rc = sample_passes(c, total, PX_SAMPLE_BYTES, e, [&](unsigned long long q0, unsigned long long q1) {
-                hipError_t pe = hipMemsetAsync(c->d_queue_px, 0, QUEUE_CTRL_BYTES, st);
+                double* smp = c->d_px_samples.as<double>();
+                uint32_t* sseg = c->d_px_sseg.as<uint32_t>();
+                hipError_t pe = hipMemsetAsync(P.queue, 0, QUEUE_CTRL_BYTES, st);
                 if (pe == hipSuccess)
-                    pe = launch_pixels_f64(P, lds, st, jobs, off, num_jobs, total, q0, (int)(q1 - q0), c->d_px_samples,
-                                          c->d_px_sseg, c->n_cu, moments ? c->tuning.grid_workgroups : 0);
+                    pe = launch_pixels_f64(P, lds, st, jobs, off, num_jobs, total, q0, (int)(q1 - q0), smp, sseg, c->n_cu,
+                                           moments ? c->tuning.grid_workgroups : 0);
                 if (pe == hipSuccess)
-                    pe = moments ? launch_pixels_reduce_moments(off, num_jobs, q0, q1, c->d_px_samples, c->d_px_sseg, acc,
-                                                                (double*)out_sums, (double*)out_sumsq, out_segments, st)
-                                 : launch_pixels_reduce(off, num_jobs, q0, q1, c->d_px_samples, c->d_px_sseg, acc,
-                                                        (double*)out_sums, out_segments, st);
+                    pe = moments ? launch_pixels_reduce_moments(off, num_jobs, q0, q1, smp, sseg, acc, (double*)out_sums,
+                                                                (double*)out_sumsq, out_segments, st)
+                                 : launch_pixels_reduce(off, num_jobs, q0, q1, smp, sseg, acc, (double*)out_sums,
+                                                        out_segments, st);
                 return pe;
             });
             if (rc) return rc;
         }
     }
-    if (e != hipSuccess) return fail(c, RT_ERR_HIP, "pixel render launch: %s", hipGetErrorString(e));
-    HIPCHK(c, hipEventRecord(c->ev1, st));
-    c->timed = true;
-    return RT_OK;
+    return timed_end(c, st, e, "pixel render launch");
 }
 
 int rt_render_pixels(rt_ctx* c, const rt_camera* cam, const rt_pixel_job* jobs, int num_jobs, int max_depth,
@@ -1333,44 +1280,43 @@ int rt_render_pixels_aov(rt_ctx* c, const rt_camera* cam, const rt_pixel_job* jo
     const hipStream_t st = q.st;
     const rt_aov_buffers o = *out;
     const int acc = accumulate ? 1 : 0;
-    const unsigned long long* off = c->d_px_offsets;
-    if ((rc = grow(c, &c->d_aov_near, &c->aov_near_cap, nj * 16))) return rc;
+    const unsigned long long* off = c->d_px_offsets.as<unsigned long long>();
+    const int* remap = c->scene.d_remap.as<int>();
+    if ((rc = reserve(c, c->d_aov_near, nj * 16))) return rc;
     hipError_t e = hipSuccess;
     if (c->precision != RT_PREC_F64) {
         // albedo's sums and flags, then normal's, in rt_render_pixels' scratch
-        if ((rc = grow(c, (void**)&c->d_px_acc, &c->px_acc_cap, nj * 6 * sizeof(long long)))) return rc;
-        if ((rc = grow(c, (void**)&c->d_px_flags, &c->px_flags_cap, nj * 2 * sizeof(uint32_t)))) return rc;
-        long long* acc_a = o.albedo ? c->d_px_acc : nullptr;
-        long long* acc_n = o.normal ? c->d_px_acc + nj * 3 : nullptr;
-        uint32_t *fl_a = c->d_px_flags, *fl_n = c->d_px_flags + nj;
-        unsigned long long* near = (o.depth || o.id) ? (unsigned long long*)c->d_aov_near : nullptr;
+        if ((rc = reserve(c, c->d_px_acc, nj * 6 * sizeof(long long)))) return rc;
+        if ((rc = reserve(c, c->d_px_flags, nj * 2 * sizeof(uint32_t)))) return rc;
+        long long* acc_a = o.albedo ? c->d_px_acc.as<long long>() : nullptr;
+        long long* acc_n = o.normal ? c->d_px_acc.as<long long>() + nj * 3 : nullptr;
+        uint32_t *fl_a = c->d_px_flags.as<uint32_t>(), *fl_n = c->d_px_flags.as<uint32_t>() + nj;
+        unsigned long long* near = (o.depth || o.id) ? c->d_aov_near.as<unsigned long long>() : nullptr;
         if (acc_a) e = launch_pixels_seed(off, num_jobs, acc, (const float*)o.albedo, acc_a, fl_a, nullptr, st);
         if (e == hipSuccess && acc_n)
             e = launch_pixels_seed(off, num_jobs, acc, (const float*)o.normal, acc_n, fl_n, nullptr, st);
         if (e == hipSuccess && (near || o.hits))
             e = launch_aov_seed(off, num_jobs, acc, (const float*)o.depth, o.id, near, o.hits, st);
         if (e == hipSuccess)
-            e = launch_aov_f32(P, lds, st, jobs, off, num_jobs, total, c->d_remap, (unsigned long long*)acc_a, fl_a,
+            e = launch_aov_f32(P, lds, st, jobs, off, num_jobs, total, remap, (unsigned long long*)acc_a, fl_a,
                                (unsigned long long*)acc_n, fl_n, near, o.hits, c->n_cu, c->aov_combine != 0);
         if (e == hipSuccess && acc_a) e = launch_pixels_finalize(off, num_jobs, acc, acc_a, fl_a, (float*)o.albedo, st);
         if (e == hipSuccess && acc_n) e = launch_pixels_finalize(off, num_jobs, acc, acc_n, fl_n, (float*)o.normal, st);
         if (e == hipSuccess && near) e = launch_aov_finalize(off, num_jobs, acc, near, (float*)o.depth, o.id, st);
     } else {
         rc = sample_passes(c, total, AOV_SAMPLE_BYTES, e, [&](unsigned long long q0, unsigned long long q1) {
-            const hipError_t pe = launch_aov_f64(P, lds, st, jobs, off, num_jobs, total, q0, (int)(q1 - q0), c->d_remap,
-                                                 c->d_px_samples, (int32_t*)c->d_px_sseg, c->n_cu);
+            double* smp = c->d_px_samples.as<double>();
+            int32_t* sid = c->d_px_sseg.as<int32_t>();
+            const hipError_t pe =
+                launch_aov_f64(P, lds, st, jobs, off, num_jobs, total, q0, (int)(q1 - q0), remap, smp, sid, c->n_cu);
             return pe != hipSuccess
                        ? pe
-                       : launch_aov_reduce(off, num_jobs, q0, q1, c->d_px_samples, (const int32_t*)c->d_px_sseg, acc,
-                                           c->d_aov_near, (double*)o.albedo, (double*)o.normal, (double*)o.depth, o.id,
-                                           o.hits, st);
+                       : launch_aov_reduce(off, num_jobs, q0, q1, smp, sid, acc, c->d_aov_near.p, (double*)o.albedo,
+                                           (double*)o.normal, (double*)o.depth, o.id, o.hits, st);
         });
         if (rc) return rc;
     }
-    if (e != hipSuccess) return fail(c, RT_ERR_HIP, "aov launch: %s", hipGetErrorString(e));
-    HIPCHK(c, hipEventRecord(c->ev1, st));
-    c->timed = true;
-    return RT_OK;
+    return timed_end(c, st, e, "aov launch");
 }
 
 int rt_refine_jobs(rt_ctx* c, rt_pixel_job* jobs, int num_jobs, const void* sums, const void* sumsq,
@@ -1389,30 +1335,27 @@ int rt_refine_jobs(rt_ctx* c, rt_pixel_job* jobs, int num_jobs, const void* sums
                     ap->rel_error, ap->abs_floor);
     if (!stats) return RT_OK;   // (no jobs, nothing to count)
     HIPCHK(c, hipSetDevice(c->device));
-    hipStream_t st = stream ? (hipStream_t)stream : c->stream;
+    hipStream_t st = stream_of(c, stream);
     HIPCHK(c, hipEventRecord(c->ev0, st));
     hipError_t e = hipMemsetAsync(stats, 0, 2 * sizeof(uint64_t), st);
     if (e == hipSuccess && num_jobs > 0)
         e = launch_refine_jobs(jobs, num_jobs, sums, sumsq, (int)elem_bytes(c), ap->rel_error, ap->abs_floor,
                                ap->min_samples, ap->max_samples, ap->max_step, (unsigned long long*)stats, st);
-    if (e != hipSuccess) return fail(c, RT_ERR_HIP, "refine launch: %s", hipGetErrorString(e));
-    HIPCHK(c, hipEventRecord(c->ev1, st));
-    c->timed = true;
-    return RT_OK;
+    return timed_end(c, st, e, "refine launch");
 }
 
 int rt_trace_rays_diag(rt_ctx* c, const void* rays, int n, rt_hit* hits, uint64_t counters[4]) {
     if (!c || !counters) return RT_ERR_INVALID;
-    if (c->precision != RT_PREC_F32 || c->n_mnodes > 0)
+    if (c->precision != RT_PREC_F32 || c->scene.n_mnodes > 0)
         return fail(c, RT_ERR_INVALID, "rt_trace_rays_diag instruments the fp32 sphere-scene kernel");
-    unsigned long long* d = nullptr;
-    HIPCHK(c, hipMalloc((void**)&d, DIAG_SLOTS * sizeof(unsigned long long)));
+    DevBuf counts;
+    HIPCHK(c, counts.reserve(DIAG_SLOTS * sizeof(unsigned long long)));
+    unsigned long long* d = counts.as<unsigned long long>();
     hipError_t e = hipMemsetAsync(d, 0, DIAG_SLOTS * sizeof(unsigned long long), c->stream);
     int rc = e == hipSuccess ? trace_rays(c, rays, n, nullptr, hits, c->stream, d) : RT_OK;
     unsigned long long h[DIAG_SLOTS] = {};
     if (e == hipSuccess && rc == RT_OK) e = hipMemcpyAsync(h, d, sizeof(h), hipMemcpyDeviceToHost, c->stream);
     if (e == hipSuccess && rc == RT_OK) e = hipStreamSynchronize(c->stream);
-    (void)hipFree(d);
     if (rc) return rc;
     if (e != hipSuccess) return fail(c, RT_ERR_HIP, "trace diag: %s", hipGetErrorString(e));
     for (int k = 0; k < 4; ++k) counters[k] = h[2 + k];   // inner_it, inner_act, leaf_it, leaf_act
@@ -1428,28 +1371,28 @@ int rt_render_diag_ex(rt_ctx* c, const rt_camera* cam, int spp, int max_depth, u
     if (!c || !counters || n < 1 || n > DIAG_SLOTS)
         return c ? fail(c, RT_ERR_INVALID, "rt_render_diag_ex: counters and 1 <= n <= %d", DIAG_SLOTS) : RT_ERR_INVALID;
     if (c->precision != RT_PREC_F32) return fail(c, RT_ERR_INVALID, "rt_render_diag instruments the fp32 kernel");
-    if (!c->has_scene) return fail(c, RT_ERR_NO_SCENE, "no scene");
+    if (!c->scene.has_scene) return fail(c, RT_ERR_NO_SCENE, "no scene");
     if (spp > FIX_LAUNCH_SAMPLES) return fail(c, RT_ERR_INVALID, "rt_render_diag: spp <= %d", FIX_LAUNCH_SAMPLES);
     int rc = check_camera(c, cam);
     if (rc) return rc;
     HIPCHK(c, hipSetDevice(c->device));
     rt_shard_info si;
     rt_shard_layout(cam->image_width, cam->image_height, 0, 1, &si);
-    if ((rc = grow(c, &c->d_shard, &c->shard_cap, (size_t)si.num_tiles * 64 * 3 * 4))) return rc;
-    unsigned long long* d = nullptr;
-    HIPCHK(c, hipMalloc((void**)&d, DIAG_SLOTS * sizeof(unsigned long long)));
+    if ((rc = reserve(c, c->d_shard, (size_t)si.num_tiles * 64 * 3 * 4))) return rc;
+    DevBuf counts;
+    HIPCHK(c, counts.reserve(DIAG_SLOTS * sizeof(unsigned long long)));
+    unsigned long long* d = counts.as<unsigned long long>();
     hipError_t e = hipMemsetAsync(d, 0, DIAG_SLOTS * sizeof(unsigned long long), c->stream);
     // the persistent kernel of rt_render, instrumented (block 512, <= 64 VGPRs; the
     // coherent-primary kernel at the context's block, 512 or 1024; the ray pool at 512)
     // exactly the kernel rt_render runs for this tuning, instrumented (RT_DIAG_VARIANTS);
     // a tuning with no instrumented build is refused (RT_ERR_INVALID), never substituted
     c->diag_buf = d;
-    if (e == hipSuccess) rc = rt_render(c, cam, spp, max_depth, 0, 1, c->d_shard, nullptr, nullptr);
+    if (e == hipSuccess) rc = rt_render(c, cam, spp, max_depth, 0, 1, c->d_shard.p, nullptr, nullptr);
     c->diag_buf = nullptr;
     if (e == hipSuccess && rc == RT_OK)
         e = hipMemcpyAsync(counters, d, (size_t)n * sizeof(unsigned long long), hipMemcpyDeviceToHost, c->stream);
     if (e == hipSuccess && rc == RT_OK) e = hipStreamSynchronize(c->stream);
-    (void)hipFree(d);
     if (rc) return rc;
     if (e != hipSuccess) return fail(c, RT_ERR_HIP, "diag render: %s", hipGetErrorString(e));
     return RT_OK;
@@ -1458,23 +1401,24 @@ int rt_render_diag_ex(rt_ctx* c, const rt_camera* cam, int spp, int max_depth, u
 int rt_trace_tape(rt_ctx* c, const double ray[7], int depth, const double* tape, int tape_len, double out[3],
                   int* used) {
     if (!c || !ray || !out || !used || tape_len < 0 || (tape_len > 0 && !tape)) return RT_ERR_INVALID;
-    if (!c->has_scene) return fail(c, RT_ERR_NO_SCENE, "rt_trace_tape before rt_upload_scene");
+    if (!c->scene.has_scene) return fail(c, RT_ERR_NO_SCENE, "rt_trace_tape before rt_upload_scene");
     if (c->precision != RT_PREC_F64) return fail(c, RT_ERR_INVALID, "rt_trace_tape needs an RT_PREC_F64 context");
     if (depth > 64) return fail(c, RT_ERR_LIMIT, "depth %d > 64", depth);
     HIPCHK(c, hipSetDevice(c->device));
     int rc;
-    if ((rc = grow(c, (void**)&c->d_tape, &c->tape_cap, (size_t)(tape_len > 0 ? tape_len : 1) * sizeof(double))))
+    if ((rc = reserve(c, c->d_tape, (size_t)(tape_len > 0 ? tape_len : 1) * sizeof(double))))
         return rc;
     if (tape_len)
-        HIPCHK(c, hipMemcpyAsync(c->d_tape, tape, (size_t)tape_len * sizeof(double), hipMemcpyHostToDevice, c->stream));
-    HIPCHK(c, hipMemcpyAsync(c->d_small, ray, 7 * sizeof(double), hipMemcpyHostToDevice, c->stream));
+        HIPCHK(c, hipMemcpyAsync(c->d_tape.p, tape, (size_t)tape_len * sizeof(double), hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipMemcpyAsync(c->d_small.p, ray, 7 * sizeof(double), hipMemcpyHostToDevice, c->stream));
     rt_camera dummy{};
     dummy.image_width = dummy.image_height = 1;
     RenderParams P;
     fill_params(c, &dummy, 1, depth, plan_launch(c, true).mesh_stack, P);
-    HIPCHK(c, launch_tape_f64(P, depth, c->d_small, c->d_tape, tape_len, c->d_small + 8, c->d_used, c->stream));
-    HIPCHK(c, hipMemcpyAsync(out, c->d_small + 8, 3 * sizeof(double), hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipMemcpyAsync(used, c->d_used, sizeof(int), hipMemcpyDeviceToHost, c->stream));
+    double* small = c->d_small.as<double>();
+    HIPCHK(c, launch_tape_f64(P, depth, small, c->d_tape.as<double>(), tape_len, small + 8, c->d_used.as<int>(), c->stream));
+    HIPCHK(c, hipMemcpyAsync(out, small + 8, 3 * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipMemcpyAsync(used, c->d_used.p, sizeof(int), hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
     return RT_OK;
 }

@@ -50,7 +50,7 @@ ncclResult_t wait_comm(ncclComm_t comm, int timeout_ms) {
 
 }  // namespace
 
-void rt_comm_release(rt_ctx* c) {
+void rt_comm_release(rt_ctx_base* c) {
     if (c && c->comm) {
         (void)ncclCommDestroy((ncclComm_t)c->comm);
         c->comm = nullptr;
@@ -163,7 +163,7 @@ int rt_comm_gather_group(rt_ctx** cs, int n, size_t elems, void* gathered) {
             return fail(cs[0], RT_ERR_INVALID, "context %d is not rank %d of an %d-rank communicator", r, r, n);
     NCCLCHK(cs[0], ncclGroupStart());
     for (int r = 0; r < n; ++r) {
-        const ncclResult_t e = ncclGather(cs[r]->d_shard, r == 0 ? gathered : nullptr, elems, dtype_of(cs[r]), 0,
+        const ncclResult_t e = ncclGather(cs[r]->d_shard.p, r == 0 ? gathered : nullptr, elems, dtype_of(cs[r]), 0,
                                           (ncclComm_t)cs[r]->comm, cs[r]->stream);
         if (e != ncclSuccess) {
             (void)ncclGroupEnd();

@@ -13,13 +13,20 @@
 #include <vector>
 
 #include "../../include/rt_hip.h"
+#include "rt_devbuf.h"
 #include "rt_device.h"
 #include "rt_lbvh.h"
 #include "rt_pack.h"
 
 using namespace rtx;
 
-struct rt_ctx {
+// What a context owns, and the order it goes in (rt_destroy is `delete`): ~rt_ctx's body makes
+// the device current, waits for the context's stream and frees the pinned staging buffer; then
+// rt_ctx's members go, which is every byte of device memory (DevBuf: the scene, the mesh
+// builder's scratch, the scratch of the calls, the Accum slots); then the base, ~rt_ctx_base:
+// the communicator, the events, the stream.  A DevBuf member added to rt_ctx is freed with the
+// rest, in that place; the base holds no device memory.
+struct rt_ctx_base {
     int device = 0;
     int precision = RT_PREC_F32;
     uint64_t seed = 0;
@@ -27,25 +34,49 @@ struct rt_ctx {
     hipEvent_t ev0 = nullptr, ev1 = nullptr;
     bool timed = false;
     std::string err;
+    // RCCL communicator (rt_comm_init_rank / rt_comm_init_all): rank comm_rank of comm_size
+    void* comm = nullptr;   // ncclComm_t
+    int comm_rank = 0, comm_size = 0;
+    bool comm_nonblocking = false;   // made by rt_comm_init_rank[_timeout] (ncclConfig_t.blocking = 0)
+
+    rt_ctx_base() = default;
+    rt_ctx_base(const rt_ctx_base&) = delete;
+    ~rt_ctx_base();   // rt_abi.cpp
+};
+
+struct rt_ctx : rt_ctx_base {
+    ~rt_ctx();   // rt_abi.cpp
+
     // measured best (tools/sweep.py, tools/mesh_sweep.py; profiles/r01)
     rt_tuning tuning{1024, 6, 1.0, 0.25, 8, RT_TRAV_DEFAULT, 2, -1, 2.0, 65536, 16384, RT_MESH_BUILD_HOST, -1, -1, 0, 32, 8.0, 20.0, 48, 0, 0, -1, 2.0, 32};
 
-    // scene (device)
-    bool has_scene = false;
-    Node* d_nodes = nullptr;
-    void* d_sph = nullptr;
-    void* d_mat = nullptr;
-    SphereD* d_big = nullptr;
-    BigF* d_bigf = nullptr;     // the big spheres relative to their near points (fp32 kernels)
-    int n_nodes = 0, n_sph = 0, n_mat = 0, n_big = 0, depth = 0, leaves = 0, n_input = 0;
-    int n_front = 0;   // spheres [0, n_front) are tested before the BVH (rt_tuning.front_spheres)
-    float box_extent = 0.f;   // bound of |coordinate| over the node boxes (RenderParams::box_extent)
-    void* d_grid = nullptr;     // fp32: the uniform sphere grid (GridHdr ...), when the scene suits one
-    int grid_nodes = 0;         // its size in sizeof(Node) units (it takes the nodes' LDS region)
-    GridHdr grid_hdr{};         // its header (RenderParams::grid)
-    int grid_entries = 0;       // sphere references over its cells
-    double grid_density = 0.0;  // the sphere_grid_density it was built with (rt_scene_info, ABI 10)
-    SceneReach reach;           // where a launch's rays can start (rt_pack.h grid_reach_ok)
+    // The uploaded scene, device buffers and host facts together: rt_upload_scene_ex fills a
+    // local one and moves it in, and `scene = Scene{}` forgets all of it at once.
+    struct Scene {
+        bool has_scene = false;
+        DevBuf d_nodes;     // Node
+        DevBuf d_sph;       // SphereF | SphereD
+        DevBuf d_mat;       // MatF | MatD
+        DevBuf d_big;       // SphereD
+        DevBuf d_bigf;      // BigF: the big spheres relative to their near points (fp32 kernels)
+        int n_nodes = 0, n_sph = 0, n_mat = 0, n_big = 0, depth = 0, leaves = 0, n_input = 0;
+        int n_front = 0;   // spheres [0, n_front) are tested before the BVH (rt_tuning.front_spheres)
+        float box_extent = 0.f;   // bound of |coordinate| over the node boxes (RenderParams::box_extent)
+        DevBuf d_grid;              // fp32: the uniform sphere grid (GridHdr ...), when the scene suits one
+        int grid_nodes = 0;         // its size in sizeof(Node) units (it takes the nodes' LDS region)
+        GridHdr grid_hdr{};         // its header (RenderParams::grid)
+        int grid_entries = 0;       // sphere references over its cells
+        double grid_density = 0.0;  // the sphere_grid_density it was built with (rt_scene_info, ABI 10)
+        SceneReach reach;           // where a launch's rays can start (rt_pack.h grid_reach_ok)
+        DevBuf d_remap;     // int; rt_trace_rays: kernel id slot -> input index (spheres | big | triangles)
+        DevBuf d_unmap;     // int; rt_trace_rays_from: input index -> Hit::id (d_remap's inverse), n_unmap entries
+        int n_unmap = 0;
+        DevBuf d_mnodes;    // Node4; mesh BVH (4-wide) + triangles (HBM-resident)
+        DevBuf d_tris;      // TriF | TriD
+        DevBuf d_tmeta;     // uint32_t; fp32: per-triangle meta words (leaf order), beside the 48-B TriF records
+        int n_mnodes = 0, n_tris = 0, mdepth = 0, mleaves = 0;
+        float mbox[6] = {};         // the mesh's box (lo xyz, hi xyz): union of the root's child boxes
+    } scene;
     // r07: resumable flat grid walks (RenderParams::gsus_lanes / gsus_iters), from the
     // environment's RT_GRID_SUSPEND at rt_create
     int gsus_lanes = GSUS_DEFAULT_LANES, gsus_iters = GSUS_DEFAULT_ITERS;
@@ -55,97 +86,63 @@ struct rt_ctx {
     // r10: waiting lanes adopt their own batch hits (RenderParams::batch_adopt), from the
     // environment's RT_BATCH_ADOPT at rt_create
     int batch_adopt = 1;
-    int* d_remap = nullptr;     // rt_trace_rays: kernel id slot -> input index (spheres | big | triangles)
-    int* d_unmap = nullptr;     // rt_trace_rays_from: input index -> Hit::id (d_remap's inverse), n_unmap entries
-    int n_unmap = 0;
-    Node4* d_mnodes = nullptr;  // mesh BVH (4-wide) + triangles (HBM-resident)
-    void* d_tris = nullptr;
-    uint32_t* d_tmeta = nullptr;   // fp32: per-triangle meta words (leaf order), beside the 48-B TriF records
-    int n_mnodes = 0, n_tris = 0, mdepth = 0, mleaves = 0;
-    float mbox[6] = {};         // the mesh's box (lo xyz, hi xyz): union of the root's child boxes
     LbvhScratch lbvh;           // GPU mesh-BVH build scratch
 
     // scratch for the host-in/host-out paths (grown on demand, outside timed code)
-    void* d_shard = nullptr;
-    size_t shard_cap = 0;
-    void* d_frame = nullptr;
-    size_t frame_cap = 0;
-    uint32_t* d_segs = nullptr;
-    size_t segs_cap = 0;
-    uint32_t* d_segs_frame = nullptr;
-    size_t segs_frame_cap = 0;
-    int32_t* d_rgb = nullptr;
-    size_t rgb_cap = 0;
-    double* d_tape = nullptr;
-    size_t tape_cap = 0;
-    double* d_small = nullptr;  // ray7 + out3
-    int* d_used = nullptr;
-    void* d_samples = nullptr;  // per-sample radiance of chunked launches
-    uint32_t* d_queue64 = nullptr;   // fp64 persistent lanes (f64_kernel 3): work-queue control block
-    uint32_t* d_queue_rad = nullptr;   // rt_radiance_rays: the launch's per-XCD heads (a control block of its own)
-    size_t samples_cap = 0;
+    DevBuf d_shard, d_frame;
+    DevBuf d_segs, d_segs_frame;   // uint32_t
+    DevBuf d_rgb;                  // int32_t
+    DevBuf d_tape;                 // double
+    DevBuf d_small;                // double: ray7 + out3
+    DevBuf d_used;                 // int
+    DevBuf d_samples;              // per-sample radiance of chunked launches
+    DevBuf d_queue64;     // fp64 persistent lanes (f64_kernel 3): work-queue control block
+    DevBuf d_queue_rad;   // rt_radiance_rays: the launch's per-XCD heads (a control block of its own)
     // rt_render_pixels / rt_camera_rays (grown on demand): the scan's offsets (num_jobs + 1 x 8 B)
     // and work space, a control block of per-XCD heads of their own, fp32: the per-job
     // fixed-point sums (num_jobs x 3) and flags, fp64: one pass's samples (x 3 doubles) and
     // segment counts
-    unsigned long long* d_px_offsets = nullptr;
-    size_t px_offsets_cap = 0;
-    void* d_px_scan = nullptr;
-    size_t px_scan_cap = 0;
-    uint32_t* d_queue_px = nullptr;
-    long long* d_px_acc = nullptr;
-    size_t px_acc_cap = 0;
-    uint32_t* d_px_flags = nullptr;
-    size_t px_flags_cap = 0;
-    double* d_px_samples = nullptr;
-    size_t px_samples_cap = 0;
-    uint32_t* d_px_sseg = nullptr;
-    size_t px_sseg_cap = 0;
+    DevBuf d_px_offsets;   // unsigned long long
+    DevBuf d_px_scan;
+    DevBuf d_queue_px;
+    DevBuf d_px_acc;       // long long
+    DevBuf d_px_flags;     // uint32_t
+    DevBuf d_px_samples;   // double
+    DevBuf d_px_sseg;      // uint32_t
     // rt_render_pixels_moments, fp32: the second moments' two words per job and channel
     // (num_jobs x 6) and their flags
-    unsigned long long* d_px_sq = nullptr;
-    size_t px_sq_cap = 0;
-    uint32_t* d_px_sqflags = nullptr;
-    size_t px_sqflags_cap = 0;
+    DevBuf d_px_sq;        // unsigned long long
+    DevBuf d_px_sqflags;   // uint32_t
     // rt_render_pixels_aov: the per-job nearest hit (num_jobs x 16 B: fp32 one packed word, fp64
     // the (t, id) carried between passes); its sums use d_px_acc / d_px_flags twice over, its
     // fp64 records d_px_samples / d_px_sseg.  aov_combine: the wave combine before the atomics,
     // from the environment's RT_AOV_COMBINE at rt_create
-    void* d_aov_near = nullptr;
-    size_t aov_near_cap = 0;
+    DevBuf d_aov_near;
     int aov_combine = 1;
-    void* d_gather = nullptr;  // rt_render_frame_multi: all contexts' shards
-    size_t gather_cap = 0;
+    DevBuf d_gather;  // rt_render_frame_multi: all contexts' shards
 
     // fp32 fixed-point pixel sums (RenderParams::accum), one slot per output buffer the
     // context renders into: rt_render_range(accumulate=1) continues a slot exactly.
     struct Accum {
         const void* out = nullptr;   // the out_sums buffer these sums belong to
         int W = 0, H = 0, shard = 0, nshards = 0;
-        long long* acc = nullptr;    // npx * 3
-        uint32_t* flags = nullptr;   // npx
-        uint32_t* queue = nullptr;   // persistent-lane work counter of launches into this buffer
-        unsigned long long* accp = nullptr;   // npx * 2: one launch's packed sums
-        size_t acc_cap = 0, flags_cap = 0, accp_cap = 0;
+        DevBuf acc;     // long long, npx * 3
+        DevBuf flags;   // uint32_t, npx
+        DevBuf queue;   // persistent-lane work counter of launches into this buffer
+        DevBuf accp;    // unsigned long long, npx * 2: one launch's packed sums
         uint64_t used = 0;           // LRU stamp
     };
     static constexpr int ACCUM_SLOTS = 4;
     Accum accum[ACCUM_SLOTS];
     uint64_t accum_clock = 0;
     int n_cu = 0;                  // compute units of the device
-    unsigned long long* diag_buf = nullptr;   // set only inside rt_render_diag: the instrumented kernel runs
+    unsigned long long* diag_buf = nullptr;   // set only inside rt_render_diag: the instrumented kernel runs (not owned)
 
     // 8-bit host-bound frames (rt_finish_frame_u8 / rt_render_frame_u8): device frame and
     // a pinned host staging buffer (DMA-able, so the copy runs at full PCIe rate)
-    uint8_t* d_rgb8 = nullptr;
-    size_t rgb8_cap = 0;
+    DevBuf d_rgb8;   // uint8_t
     void* h_pinned = nullptr;
     size_t pinned_cap = 0;
-
-    // RCCL communicator (rt_comm_init_rank / rt_comm_init_all): rank comm_rank of comm_size
-    void* comm = nullptr;   // ncclComm_t
-    int comm_rank = 0, comm_size = 0;
-    bool comm_nonblocking = false;   // made by rt_comm_init_rank[_timeout] (ncclConfig_t.blocking = 0)
 };
 
 namespace rtx_abi {
@@ -166,13 +163,8 @@ inline int fail(rt_ctx* c, int code, const char* fmt, ...) {
         if (e_ != hipSuccess) return fail(ctx, RT_ERR_HIP, "%s: %s", #expr, hipGetErrorString(e_));   \
     } while (0)
 
-inline int grow(rt_ctx* c, void** p, size_t* cap, size_t bytes) {
-    if (*cap >= bytes && *p) return RT_OK;
-    if (*p) HIPCHK(c, hipFree(*p));
-    *p = nullptr;
-    *cap = 0;
-    HIPCHK(c, hipMalloc(p, bytes ? bytes : 16));
-    *cap = bytes;
+inline int reserve(rt_ctx* c, DevBuf& b, size_t bytes) {
+    HIPCHK(c, b.reserve(bytes));
     return RT_OK;
 }
 
@@ -203,5 +195,5 @@ size_t lds_scene_bytes_at(const rt_ctx* c, int block, int tr = 0);
 
 // rt_comm.cpp: drop the context's communicator (rt_destroy); the grouped gather of
 // rt_render_frame_multi (every context rank r of n, shards in their d_shard)
-void rt_comm_release(rt_ctx* c);
+void rt_comm_release(rt_ctx_base* c);
 int rt_comm_gather_group(rt_ctx** cs, int n, size_t elems, void* gathered);

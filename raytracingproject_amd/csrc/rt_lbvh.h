@@ -7,6 +7,7 @@
 #include <cstdint>
 
 #include "../../include/rt_hip.h"
+#include "rt_devbuf.h"
 #include "rt_scene.h"
 
 namespace rtx {
@@ -23,12 +24,7 @@ struct LbvhInput {
 
 // Scratch kept by the context between builds (grown on demand).
 struct LbvhScratch {
-    void *keys = nullptr, *child = nullptr, *box = nullptr, *index = nullptr, *sort_tmp = nullptr, *scan_tmp = nullptr;
-    size_t keys_cap = 0, child_cap = 0, box_cap = 0, index_cap = 0, sort_tmp_cap = 0, scan_tmp_cap = 0;
-    void release() {
-        for (void* p : {keys, child, box, index, sort_tmp, scan_tmp}) (void)hipFree(p);
-        *this = LbvhScratch();
-    }
+    DevBuf keys, child, box, index, sort_tmp, scan_tmp;
 };
 
 struct LbvhOutput {
@@ -43,6 +39,6 @@ struct LbvhOutput {
 hipError_t lbvh_build(const LbvhInput& in, LbvhScratch& ws, LbvhOutput& out, hipStream_t stream);
 // After a build of n triangles: the device array of input triangle indices in leaf order
 // (in the scratch; valid until the next build).
-inline const uint32_t* lbvh_sorted_index(const LbvhScratch& ws, int) { return (const uint32_t*)ws.keys; }
+inline const uint32_t* lbvh_sorted_index(const LbvhScratch& ws, int) { return ws.keys.as<const uint32_t>(); }
 
 }  // namespace rtx

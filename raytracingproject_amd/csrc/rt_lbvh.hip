@@ -349,33 +349,24 @@ hipError_t lbvh_build(const LbvhInput& in, LbvhScratch& ws, LbvhOutput& out, hip
     const int n = in.n;
     const unsigned B = 256, G = (unsigned)((n + B - 1) / B), Gi = (unsigned)((n > 1 ? n - 1 : 1) + B - 1) / B;
     // scratch (grown on demand, kept for rebuilds)
-    auto need = [&](void** p, size_t* cap, size_t bytes) -> hipError_t {
-        if (*cap >= bytes && *p) return hipSuccess;
-        if (*p) CHK(hipFree(*p));
-        *p = nullptr;
-        *cap = 0;
-        CHK(hipMalloc(p, bytes ? bytes : 16));
-        *cap = bytes;
-        return hipSuccess;
-    };
     const size_t nn = (size_t)(n > 1 ? 2 * n - 1 : 1), ni = (size_t)(n > 1 ? n - 1 : 1);
-    CHK(need(&ws.keys, &ws.keys_cap, (size_t)n * 4 * 4));
-    CHK(need(&ws.child, &ws.child_cap, ni * 2 * 4 + nn * 2 * 4));
-    CHK(need(&ws.box, &ws.box_cap, nn * 6 * 4 + nn * 4 * 4));
-    CHK(need(&ws.index, &ws.index_cap, ni * 4 * 3 + 64 + 4 * 260));
-    uint32_t* keys = (uint32_t*)ws.keys;
+    CHK(ws.keys.reserve((size_t)n * 4 * 4));
+    CHK(ws.child.reserve(ni * 2 * 4 + nn * 2 * 4));
+    CHK(ws.box.reserve(nn * 6 * 4 + nn * 4 * 4));
+    CHK(ws.index.reserve(ni * 4 * 3 + 64 + 4 * 260));
+    uint32_t* keys = ws.keys.as<uint32_t>();
     uint32_t* keys_s = keys + n;
     uint32_t* vals = keys + 2 * (size_t)n;
     uint32_t* vals_s = keys + 3 * (size_t)n;
     uint32_t* lidx = keys;                                       // after the sort: input index by leaf position
-    uint32_t* child = (uint32_t*)ws.child;                       // 2(n-1)
+    uint32_t* child = ws.child.as<uint32_t>();                   // 2(n-1)
     uint32_t* range = child + 2 * ni;                            // 2(2n-1): every node's [first, last]
-    float* box = (float*)ws.box;                                 // 6(2n-1)
+    float* box = ws.box.as<float>();                             // 6(2n-1)
     uint32_t* parent = (uint32_t*)(box + nn * 6);                // 2n-1
     float* cost = (float*)(parent + nn);                         // 2n-1
     uint32_t* count = (uint32_t*)(cost + nn);                    // 2n-1
     uint32_t* off = count + nn;                                  // 2n-1
-    uint32_t* keep = (uint32_t*)ws.index;                        // n-1
+    uint32_t* keep = ws.index.as<uint32_t>();                    // n-1
     uint32_t* index = keep + ni;                                 // n-1
     int* depth = (int*)(index + ni);                             // n-1
     int* counters = depth + ni;   // [0] max live depth, [1] leaves, [2] max depth; [4..] treelet roots per depth
@@ -387,8 +378,8 @@ hipError_t lbvh_build(const LbvhInput& in, LbvhScratch& ws, LbvhOutput& out, hip
     CHK(hipGetLastError());
     size_t tmp = 0;
     CHK(rocprim::radix_sort_pairs(nullptr, tmp, keys, keys_s, vals, vals_s, (size_t)n, 0, 30, st));
-    CHK(need(&ws.sort_tmp, &ws.sort_tmp_cap, tmp));
-    CHK(rocprim::radix_sort_pairs(ws.sort_tmp, tmp, keys, keys_s, vals, vals_s, (size_t)n, 0, 30, st));
+    CHK(ws.sort_tmp.reserve(tmp));
+    CHK(rocprim::radix_sort_pairs(ws.sort_tmp.p, tmp, keys, keys_s, vals, vals_s, (size_t)n, 0, 30, st));
     CHK(hipMemsetAsync(counters, 0, 16, st));
     CHK(hipMemsetAsync(off, 0, nn * 4, st));   // (the root's position: 0)
     hipLaunchKernelGGL(leaf_boxes, dim3(G), dim3(B), 0, st, in.tris, vals_s, n, box, cost, count);
@@ -460,8 +451,8 @@ hipError_t lbvh_build(const LbvhInput& in, LbvhScratch& ws, LbvhOutput& out, hip
         CHK(hipGetLastError());
         size_t stmp = 0;
         CHK(rocprim::exclusive_scan(nullptr, stmp, keep, index, 0u, (size_t)(n - 1), rocprim::plus<uint32_t>(), st));
-        CHK(need(&ws.scan_tmp, &ws.scan_tmp_cap, stmp));
-        CHK(rocprim::exclusive_scan(ws.scan_tmp, stmp, keep, index, 0u, (size_t)(n - 1), rocprim::plus<uint32_t>(),
+        CHK(ws.scan_tmp.reserve(stmp));
+        CHK(rocprim::exclusive_scan(ws.scan_tmp.p, stmp, keep, index, 0u, (size_t)(n - 1), rocprim::plus<uint32_t>(),
                                     st));
         uint32_t last_keep = 0, last_index = 0;
         int cnt[2] = {0, 0};

@@ -18,7 +18,7 @@ namespace rtx_abi {
 // both children hit, and each pending one belongs to a distinct ancestor of the node being
 // visited, so at most `depth` (inner levels) are pending; the latest sits in a register
 // (closest_hit's `top`), the rest in LDS.
-int stack_entries(const rt_ctx* c) { return c->depth > 1 ? c->depth - 1 : 1; }
+int stack_entries(const rt_ctx* c) { return c->scene.depth > 1 ? c->scene.depth - 1 : 1; }
 
 // LDS of the sphere scene copy and the traversal stacks of one workgroup (kernel flags tr:
 // TRAV_GRID kernels hold the grid where the tree's nodes go, and no traversal stack).
@@ -27,8 +27,8 @@ size_t lds_scene_bytes_at(const rt_ctx* c, int block, int tr) {
     const size_t sph = c->precision == RT_PREC_F64 ? sizeof(SphereD) : sizeof(SphereF);
     const size_t mat = c->precision == RT_PREC_F64 ? sizeof(MatD) : sizeof(MatF);
     const size_t stack = grid ? 0 : (size_t)block * (size_t)stack_entries(c) * 2;
-    return (size_t)(grid ? c->grid_nodes : c->n_nodes) * sizeof(Node) + (size_t)c->n_sph * sph +
-           (size_t)c->n_mat * mat + (size_t)c->n_big * (sizeof(SphereD) + sizeof(BigF)) + ((stack + 15) & ~(size_t)15);
+    return (size_t)(grid ? c->scene.grid_nodes : c->scene.n_nodes) * sizeof(Node) + (size_t)c->scene.n_sph * sph +
+           (size_t)c->scene.n_mat * mat + (size_t)c->scene.n_big * (sizeof(SphereD) + sizeof(BigF)) + ((stack + 15) & ~(size_t)15);
 }
 
 
@@ -67,7 +67,7 @@ struct Planner {
     // ...and is one cell tall in y, so that its walk steps in x and z only (TRAV_GFLAT, r06),
     // unless the tuning keeps the 3-D walk (TRAV_G3D)
     bool grid_flat() const {
-        return grid_usable && c->grid_hdr.res[1] == 1 && !(c->tuning.traversal & TRAV_G3D);
+        return grid_usable && c->scene.grid_hdr.res[1] == 1 && !(c->tuning.traversal & TRAV_G3D);
     }
     int f64_kernel_of() const {
         const int k = c->tuning.f64_kernel > 0 ? c->tuning.f64_kernel
@@ -81,7 +81,7 @@ struct Planner {
     size_t lds_sphere_bytes_bt(int block, int tr) const {
         const bool f32 = c->precision == RT_PREC_F32;
         const size_t nw = (size_t)(block / 64);
-        const size_t coh = c->n_mnodes > 0 || !(tr & TRAV_COH)
+        const size_t coh = c->scene.n_mnodes > 0 || !(tr & TRAV_COH)
                                ? 0
                                : nw * coh_wave_bytes(false, (tr & TRAV_NOSUM) == 0, coh_fifo_entries(tr), !f32, false,
                                                     coh_cands(false, tr, !f32)) +
@@ -94,7 +94,7 @@ struct Planner {
     // lane's three item sums (floats) in LDS; the coherent kernel (fp32) puts its per-wave FIFO
     // + item sums and the CohConst block there instead.
     size_t lds_mesh_bytes_at(int block, int tr, int s) const {
-        if (c->n_mnodes == 0) return 0;
+        if (c->scene.n_mnodes == 0) return 0;
         const size_t stack = (size_t)block * (size_t)s * 4;
         const bool f64 = c->precision != RT_PREC_F32;
         if (tr & TRAV_COH)
@@ -110,7 +110,7 @@ struct Planner {
     // register file lets share a CU (LDS aside): 512 VGPRs per SIMD lane, 8-register granules,
     // at most 8 waves per SIMD, 4 SIMDs.
     int wgs_per_cu_bt(int block, int tr, int wpe) const {
-        const bool mesh = c->n_mnodes > 0;
+        const bool mesh = c->scene.n_mnodes > 0;
         const int v = kernel_vgprs(c->precision == RT_PREC_F64, mesh, block, wpe, tr, f64_kernel_of());
         int waves = v > 0 ? 512 / ((v + 7) & ~7) : 8;
         if (waves > 8) waves = 8;
@@ -140,7 +140,7 @@ struct Planner {
     // its traffic per launch rises 32.6 -> 38.3 GB at 4K @ 32 (profiles/r06/r06h, r06i, r06j);
     // mesh-only C4 keeps its 12 (none: +9 %).
     int mesh_stack_bt(int block, int tr, int wpe) const {
-        if (c->n_mnodes == 0) return 0;
+        if (c->scene.n_mnodes == 0) return 0;
         if (c->tuning.mesh_lds_stack >= 0) return c->tuning.mesh_lds_stack;
         if (tr & TRAV_GRID) return 0;
         const int most = occupancy_at(block, tr, wpe, 0);
@@ -173,7 +173,7 @@ struct Planner {
     // (fills block, trav and wpe; plan_launch derives the rest from them)
     LaunchPlan plan_of() const {
         int t = c->tuning.traversal;
-        if (c->precision != RT_PREC_F32 || c->n_mnodes == 0) t &= ~TRAV_MIFIF;   // fp32 mesh kernels only
+        if (c->precision != RT_PREC_F32 || c->scene.n_mnodes == 0) t &= ~TRAV_MIFIF;   // fp32 mesh kernels only
         // the if-if mesh loop is added wherever it is instantiated unless the while-while loop
         // (TRAV_MWHILE, never part of a kernel key) is asked for
         const bool want_mifif = (t & TRAV_MIFIF) || !(t & TRAV_MWHILE);
@@ -189,7 +189,7 @@ struct Planner {
         auto gflat = [&](int b, int w, int x, bool mesh) {
             return flat && (x & TRAV_GRID) && render_f32_supported(b, w, x | TRAV_GFLAT, mesh) ? x | TRAV_GFLAT : x;
         };
-        if (c->n_mnodes == 0) {
+        if (c->scene.n_mnodes == 0) {
             const int b = c->tuning.block, w = c->tuning.waves_per_eu;
             if ((t & TRAV_COH) && !(t & TRAV_NOSUM)) {
                 const size_t base = lds_scene_bytes_at(c, b, t), nw = (size_t)(b / 64);
@@ -270,7 +270,7 @@ struct Planner {
 }  // namespace
 
 LaunchPlan plan_launch(const rt_ctx* c, bool grid_in_reach) {
-    const Planner p{c, c->grid_nodes > 0 && grid_in_reach};
+    const Planner p{c, c->scene.grid_nodes > 0 && grid_in_reach};
     LaunchPlan r = p.plan_of();
     r.f64_kernel = p.f64_kernel_of();
     r.mesh_stack = p.mesh_stack_bt(r.block, r.trav, r.wpe);
