@@ -667,6 +667,78 @@ typedef struct {
 } rt_aov_buffers;
 int rt_render_pixels_aov(rt_ctx* ctx, const rt_camera* cam, const rt_pixel_job* jobs, int num_jobs,
                          int accumulate, const rt_aov_buffers* out, void* stream);
+/* The consumer of the calls above: an edge-avoiding a-trous wavelet filter (Dammertz et al. 2010;
+ * the spatial half of SVGF, Schied et al. 2017) over per-pixel sums, second moments and first-hit
+ * guides, on the device, in the context precision.  A 5x5 B3-spline kernel dilated by 1, 2, 4, ...
+ * whose taps are stopped by normal, depth and a variance-scaled luminance difference.  With
+ * iterations = 0 and no guides it is the finish of a non-uniform sample count: out = sums / n.
+ * The rule uses IEEE + - x / sqrt and comparisons only -- no exp, no pow, nothing fused -- so it is
+ * bit for bit reproducible in both precisions (tests/denoise_ref.py restates it in numpy).
+ *
+ * Layout and arguments.  All images are row-major width x height, pixel p = y width + x: the order
+ * of a full-frame job list (jobs[k].pixel = k), so the outputs of rt_render_pixels[_moments] and
+ * rt_render_pixels_aov plug in unchanged, and rt_unshard's frame does too.  T is the context
+ * precision; every operation below is done in T and rounded once, in the written order, nothing
+ * contracted; the double parameters are converted to T once.  max(a, b) is a > b ? a : b and
+ * min(a, b) is a < b ? a : b.
+ *   sums (x 3, required), sumsq (x 3, may be NULL): what rt_render_pixels_moments writes.
+ *   counts: the per-pixel n (uint32); NULL: every n = samples.
+ *   guides: may be NULL, and so may each member; id is ignored; albedo needs hits and
+ *     guide_samples >= 1.  albedo, normal and hits are the per-job SUMS of guide_samples samples,
+ *     exactly as rt_render_pixels_aov writes them.
+ *   params: NULL means rt_denoise_default_params'.
+ *   out (x 3, required; may be the sums buffer itself), out_variance (x 1, may be NULL).
+ * Prepare, per pixel:
+ *   nT = (T)n;  m_c = n > 0 ? s_c / nT : 0.
+ *   With albedo a_c = max((albedo_c + (T)(guide_samples - hits)) / (T)guide_samples, 1/64) -- a miss
+ *   counts as white; without, a_c = 1.  c_c = m_c / a_c;  L = ((c_0 + c_1) + c_2) / 3.
+ *   Variance V with sumsq and n >= 2: d_c = q_c - s_c m_c, v_c = d_c > 0 ? d_c / (T)(n - 1) : 0,
+ *   v'_c = v_c / (a_c a_c), V = ((v'_0 + v'_1) + v'_2) / ((T)3 nT) -- rt_refine_jobs' e2; n < 2: V = 0.
+ *   Without sumsq: over the in-image cells of the 3x3 window around p (k cells, row-major order, sums
+ *   from 0) mu = (sum of L) / k, mu2 = (sum of L L) / k, V = max(mu2 - mu mu, 0).
+ *   Normal: d = (N_0 N_0 + N_1 N_1) + N_2 N_2, n^ = d > 0 ? N / sqrt(d) : 0; no normal guide: n^ = 0.
+ *   Depth: z as given, +inf for sky; no depth guide: z = 0.
+ * Pass i = 0 .. iterations - 1, s = 2^i, per pixel p = (x, y), reading pass i - 1's c, V and L:
+ *   V~ = (sum of (g(dx) g(dy)) V_q) / (sum of g(dx) g(dy)) over the in-image cells of the undilated
+ *   3x3 window in row-major order, g = (1/4, 1/2, 1/4);  den = sigma_lum sqrt(V~) + lum_eps.
+ *   Taps dy = -2 .. 2 (outer loop), dx = -2 .. 2 (inner), q = (x + dx s, y + dy s); a tap outside
+ *   the image is skipped.  k = h(dx) h(dy), h = (1/16, 1/4, 3/8, 1/4, 1/16): exact in binary.
+ *   Centre tap: w = k.  Other taps: w = (k w_n) e8(x_z + x_l), where
+ *     w_n: 1 if n^_p and n^_q are both zero (so always without a normal guide); else
+ *          t = max((n^_p.x n^_q.x + n^_p.y n^_q.y) + n^_p.z n^_q.z, 0), squared normal_log2_power times;
+ *     x_z: 0 if z_p == z_q; otherwise, if either is infinite, the tap's w = 0; otherwise
+ *          |z_p - z_q| / (sigma_depth min(z_p, z_q));
+ *     x_l: |L_p - L_q| / den;
+ *     e8(x) = u^8 by three squarings of u = max(1 - x 0.125, 0): a compactly supported stand-in
+ *          for exp(-x) that needs only exact operations.
+ *   Accumulators start from 0 and add in tap order: Sw += w, Sc_c += w c_q,c, Sv += (w w) V_q.
+ *   Then c'_p = Sc / Sw, V'_p = Sv / (Sw Sw), and L is recomputed from c'.  Sw >= 9/64 always.
+ * Finish: out_c = c_c a_c; out_variance = V, the variance of the demodulated channel average.
+ *
+ * A non-finite input makes the outputs within its taps' reach unspecified; it is never a fault.
+ * Needs no scene.  Asynchronous on `stream` (NULL: the context's); no synchronisation of its own;
+ * rt_last_kernel_ms covers the whole call.  Scratch -- two ping-pong record images and one guide
+ * image, 4 T per pixel each -- is owned by the context and grown on demand: calls on one context
+ * must use one stream or be ordered.
+ * Errors: RT_ERR_INVALID for a NULL ctx, sums or out; width or height < 1 or width height > 2^31 -
+ * 1; counts NULL with samples < 1; albedo without hits or with guide_samples < 1; a parameter
+ * outside the ranges below -- nothing is written.  A failed allocation is RT_ERR_HIP.
+ * Not done here: temporal accumulation, firefly clamping, inpainting of n = 0 pixels, denoising
+ * rt_render's sharded buffers without rt_unshard.
+ * Added to ABI 12 without a version bump, as rt_occluded was. */
+typedef struct {
+    int32_t iterations;          /* 0..8; a-trous passes, step 2^i in pass i */
+    int32_t normal_log2_power;   /* 0..10; the normal weight is (n_p.n_q)^(2^k) by k squarings */
+    double  sigma_depth;         /* > 0, finite: relative depth difference that counts as 1 */
+    double  sigma_lum;           /* >= 0, finite: luminance difference in standard deviations */
+    double  lum_eps;             /* > 0, finite */
+} rt_denoise_params;
+/* The defaults: iterations 5, normal_log2_power 7, sigma_depth 0.05, sigma_lum 4, lum_eps 1e-6. */
+int rt_denoise_default_params(rt_denoise_params* p);
+int rt_denoise(rt_ctx* ctx, int width, int height,
+               const void* sums, const void* sumsq, const uint32_t* counts, int samples,
+               const rt_aov_buffers* guides, int guide_samples,
+               const rt_denoise_params* params, void* out, void* out_variance, void* stream);
 /* rt_trace_rays, instrumented (fp32 sphere scenes; synchronous): counters = {node-loop wave
  * iterations, their active lanes, sphere-loop wave iterations, their active lanes}. */
 int rt_trace_rays_diag(rt_ctx* ctx, const void* rays, int num_rays, rt_hit* hits, uint64_t counters[4]);

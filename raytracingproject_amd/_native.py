@@ -99,6 +99,12 @@ class RtAovBuffers(C.Structure):
                 ("hits", C.c_void_p)]
 
 
+class RtDenoiseParams(C.Structure):
+    """rt_denoise_params (32 B): rt_denoise's pass count, edge-stopping exponents and scales."""
+    _fields_ = [("iterations", C.c_int32), ("normal_log2_power", C.c_int32), ("sigma_depth", C.c_double),
+                ("sigma_lum", C.c_double), ("lum_eps", C.c_double)]
+
+
 SIGNATURES = {
     "rt_abi_version": (C.c_int, []),
     "rt_device_count": (C.c_int, []),
@@ -162,6 +168,10 @@ SIGNATURES = {
                                  C.c_void_p, C.c_void_p]),   # ABI 12
     "rt_render_pixels_aov": (C.c_int, [C.c_void_p, C.POINTER(RtCamera), C.c_void_p, C.c_int, C.c_int,
                                        C.POINTER(RtAovBuffers), C.c_void_p]),   # ABI 12
+    "rt_denoise_default_params": (C.c_int, [C.POINTER(RtDenoiseParams)]),   # ABI 12
+    "rt_denoise": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int,
+                             C.POINTER(RtAovBuffers), C.c_int, C.POINTER(RtDenoiseParams), C.c_void_p, C.c_void_p,
+                             C.c_void_p]),   # ABI 12
 }
 
 # rt_pixel_job (16 B): rt_render_pixels' / rt_camera_rays' job -- samples [sample_begin, +sample_count) of a pixel
@@ -679,6 +689,23 @@ class Renderer:
             return out, d_seg.cpu().numpy()[:n].view(np.uint32)
         return out
 
+    def render_pixels_moments_host(self, cam: RtCamera, jobs: np.ndarray, max_depth: int = 50):
+        """rt_render_pixels_moments through device copies: jobs (RtPixelJob[n]) -> (sums[n, 3],
+        sumsq[n, 3])."""
+        import torch
+        jobs = self._jobs(jobs)
+        n = len(jobs)
+        tdt = torch.from_numpy(np.zeros(0, self.dtype)).dtype
+        d_jobs = torch.from_numpy((jobs if n else np.zeros(1, RtPixelJob)).view(np.uint8)).to("cuda")
+        d_out = torch.full((max(1, n), 3), float("nan"), dtype=tdt, device="cuda")
+        d_sq = torch.full((max(1, n), 3), float("nan"), dtype=tdt, device="cuda")
+        stream = torch.cuda.current_stream().cuda_stream
+        torch.cuda.synchronize()
+        self.render_pixels_moments(cam, d_jobs.data_ptr(), n, max_depth, d_out.data_ptr(), d_sq.data_ptr(), None, False,
+                                   stream)
+        torch.cuda.synchronize()
+        return d_out.cpu().numpy()[:n], d_sq.cpu().numpy()[:n]
+
     def render_pixels_aov(self, cam: RtCamera, jobs_dev: int, n: int, albedo_dev: int | None = None,
                           normal_dev: int | None = None, depth_dev: int | None = None, id_dev: int | None = None,
                           hits_dev: int | None = None, accumulate: bool = False, stream: int | None = None) -> None:
@@ -711,6 +738,66 @@ class Renderer:
         torch.cuda.synchronize()
         return {"albedo": d_alb.cpu().numpy()[:n], "normal": d_nrm.cpu().numpy()[:n], "depth": d_dep.cpu().numpy()[:n],
                 "id": d_id.cpu().numpy()[:n], "hits": d_hits.cpu().numpy()[:n].view(np.uint32)}
+
+    @staticmethod
+    def denoise_params(**kw) -> RtDenoiseParams:
+        """rt_denoise_default_params, with the fields given in kw replaced."""
+        p = RtDenoiseParams()
+        if lib().rt_denoise_default_params(C.byref(p)) != RT_OK:
+            raise RtError("rt_denoise_default_params failed")
+        for k, v in kw.items():
+            if k not in dict(RtDenoiseParams._fields_):
+                raise TypeError(f"rt_denoise_params has no field {k!r}")
+            setattr(p, k, v)
+        return p
+
+    def denoise(self, width: int, height: int, sums_dev: int, out_dev: int, sumsq_dev: int | None = None,
+                counts_dev: int | None = None, samples: int = 0, albedo_dev: int | None = None,
+                normal_dev: int | None = None, depth_dev: int | None = None, hits_dev: int | None = None,
+                guide_samples: int = 0, params: RtDenoiseParams | None = None, variance_dev: int | None = None,
+                stream: int | None = None) -> None:
+        """rt_denoise on device pointers: width x height row-major images of the context precision --
+        sums and out x 3 (out may be sums), sumsq x 3, counts uint32, the guides as
+        rt_render_pixels_aov writes them (sums of guide_samples samples), variance x 1; a null
+        pointer leaves that input or output out, params None means the defaults.  Asynchronous."""
+        g = RtAovBuffers(albedo_dev or None, normal_dev or None, depth_dev or None, None, hits_dev or None)
+        self._check(self._L.rt_denoise(self.ctx, width, height, C.c_void_p(sums_dev or 0), C.c_void_p(sumsq_dev or 0),
+                                       C.c_void_p(counts_dev or 0), samples, C.byref(g), guide_samples,
+                                       C.byref(params) if params is not None else None, C.c_void_p(out_dev or 0),
+                                       C.c_void_p(variance_dev or 0), C.c_void_p(stream or 0)), "rt_denoise")
+
+    def denoise_host(self, width: int, height: int, sums: np.ndarray, sumsq: np.ndarray | None = None,
+                     counts: np.ndarray | None = None, samples: int = 0, albedo: np.ndarray | None = None,
+                     normal: np.ndarray | None = None, depth: np.ndarray | None = None,
+                     hits: np.ndarray | None = None, guide_samples: int = 0,
+                     params: RtDenoiseParams | None = None):
+        """rt_denoise through device copies: numpy images in (any shape of width x height [x 3]
+        elements, converted to the context precision; counts and hits to uint32) ->
+        (out[height x width, 3], variance[height x width])."""
+        import torch
+        npx = width * height
+
+        def dev(a, dt, per):
+            if a is None:
+                return None
+            a = np.ascontiguousarray(np.asarray(a, dtype=dt).reshape(-1))
+            if a.size != npx * per:
+                raise ValueError(f"an image of {a.size} elements for {width}x{height} x {per}")
+            return torch.from_numpy(a.view(np.uint8).copy()).to("cuda")
+
+        d_s, d_q = dev(sums, self.dtype, 3), dev(sumsq, self.dtype, 3)
+        d_n, d_h = dev(counts, np.uint32, 1), dev(hits, np.uint32, 1)
+        d_a, d_nm, d_z = dev(albedo, self.dtype, 3), dev(normal, self.dtype, 3), dev(depth, self.dtype, 1)
+        tdt = torch.from_numpy(np.zeros(0, self.dtype)).dtype
+        d_out = torch.full((npx, 3), float("nan"), dtype=tdt, device="cuda")
+        d_var = torch.full((npx,), float("nan"), dtype=tdt, device="cuda")
+        ptr = lambda t: None if t is None else t.data_ptr()  # noqa: E731
+        stream = torch.cuda.current_stream().cuda_stream
+        torch.cuda.synchronize()
+        self.denoise(width, height, ptr(d_s), d_out.data_ptr(), ptr(d_q), ptr(d_n), samples, ptr(d_a), ptr(d_nm),
+                     ptr(d_z), ptr(d_h), guide_samples, params, d_var.data_ptr(), stream)
+        torch.cuda.synchronize()
+        return d_out.cpu().numpy(), d_var.cpu().numpy()
 
     def camera_rays(self, cam: RtCamera, jobs_dev: int, n: int, rays_dev: int, keys_dev: int,
                     ray_job_dev: int | None, max_rays: int, stream: int | None = None) -> int:

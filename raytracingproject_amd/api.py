@@ -363,6 +363,41 @@ class camera:
                 "depth": o["depth"].reshape(H, W), "id": o["id"].reshape(H, W),
                 "coverage": (o["hits"].astype(o["albedo"].dtype) / dt(n)).reshape(H, W)}
 
+    def render_denoised(self, world: hittable, samples: int | None = None, counts=None, **params) -> dict:
+        """The frame at `samples` per pixel (default: samples_per_pixel), denoised on the device
+        (rt_denoise): a full-frame job list through rt_render_pixels_moments and
+        rt_render_pixels_aov, then the a-trous filter guided by albedo, normal, depth and the
+        samples' own variance.  params: rt_denoise_params' fields (iterations, normal_log2_power,
+        sigma_depth, sigma_lum, lum_eps); the rest keep the library's defaults.
+        counts: Renderer.render_adaptive's (sums, sumsq, n) -- device tensors or arrays -- in place
+        of the uniform render: the filter divides by the per-pixel n, and the guides still come
+        from samples 0 .. samples - 1.
+        -> {"color": [H, W, 3] the denoised mean, "noisy": [H, W, 3] sums / n, "variance": [H, W]
+        the filtered variance of the demodulated channel average}, in the camera's precision."""
+        self.initialize()
+        if self._renderer is None:
+            self._renderer = N.Renderer(self.device, self.seed, self.precision)
+        r = self._renderer
+        self._upload(r, world)
+        spp = self.samples_per_pixel if samples is None else samples
+        W, H = self._cam.image_width, self._cam.image_height
+        jobs = np.zeros(W * H, N.RtPixelJob)
+        jobs["pixel"], jobs["sample_count"] = np.arange(W * H), spp
+        g = r.render_pixels_aov_host(self._cam, jobs)
+        if counts is None:
+            sums, sumsq = r.render_pixels_moments_host(self._cam, jobs, self.max_depth)
+            n = None
+        else:
+            sums, sumsq, n = (a.cpu().numpy() if hasattr(a, "cpu") else np.asarray(a) for a in counts)
+            sums, sumsq = sums.reshape(-1, 3).astype(r.dtype), sumsq.reshape(-1, 3).astype(r.dtype)
+            n = n.reshape(-1).astype(np.uint32)
+        out, var = r.denoise_host(W, H, sums, sumsq, n, spp if n is None else 0, g["albedo"], g["normal"], g["depth"],
+                                  g["hits"], spp, N.Renderer.denoise_params(**params))
+        with np.errstate(divide="ignore", invalid="ignore"):
+            noisy = sums / r.dtype(spp) if n is None else np.where(n[:, None] > 0, sums / n[:, None].astype(r.dtype), 0)
+        return {"color": out.reshape(H, W, 3), "noisy": noisy.astype(r.dtype).reshape(H, W, 3),
+                "variance": var.reshape(H, W)}
+
 
 def write_ppm(out, rgb: np.ndarray) -> None:
     """PPM P3 exactly as camera.h:35 and color.h:32-34 print it."""

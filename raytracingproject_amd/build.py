@@ -32,10 +32,12 @@ UNITS = {
     "rt_bvh.cpp": ["-ffp-contract=off"],
     "rt_obj.cpp": ["-ffp-contract=off"],
     "rt_lbvh.hip": ["-ffp-contract=off"],
+    # rt_denoise's rule is bit-exact in fp32 too: no contraction, IEEE divide / sqrt, denormals kept
+    "rt_denoise.hip": ["-ffp-contract=off"],
     "rt_comm.cpp": [],
 }
 HEADERS = ["rt_device.h", "rt_render_impl.h", "rt_occluded.h", "rt_radiance.h", "rt_pixels.h", "rt_moments.h", "rt_aov.h", "rt_scene.h", "rt_launch.h", "rt_bvh.h", "rt_lbvh.h", "rt_ctx.h", "rt_devbuf.h",
-           "rt_treelet.h", "rt_pack.h", "rt_batch_cull.h"]
+           "rt_treelet.h", "rt_pack.h", "rt_batch_cull.h", "rt_denoise.h"]
 
 
 def _stale(target: Path, deps: list[Path]) -> bool:

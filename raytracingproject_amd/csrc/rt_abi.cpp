@@ -1344,6 +1344,57 @@ int rt_refine_jobs(rt_ctx* c, rt_pixel_job* jobs, int num_jobs, const void* sums
     return timed_end(c, st, e, "refine launch");
 }
 
+static const rt_denoise_params DENOISE_DEFAULTS = {5, 7, 0.05, 4.0, 1e-6};
+
+int rt_denoise_default_params(rt_denoise_params* p) {
+    if (!p) return RT_ERR_INVALID;
+    *p = DENOISE_DEFAULTS;
+    return RT_OK;
+}
+
+// rt_denoise: validation, the three record images of scratch, then rt_denoise.hip's launches
+// between the context's two events.  Nothing is launched or written before every check has passed.
+int rt_denoise(rt_ctx* c, int width, int height, const void* sums, const void* sumsq, const uint32_t* counts,
+               int samples, const rt_aov_buffers* guides, int guide_samples, const rt_denoise_params* params, void* out,
+               void* out_variance, void* stream) {
+    if (!c) return RT_ERR_INVALID;
+    if (!sums || !out) return fail(c, RT_ERR_INVALID, "rt_denoise: sums %p, out %p", sums, out);
+    if (width < 1 || height < 1 || (long long)width * height > 0x7fffffffll)
+        return fail(c, RT_ERR_INVALID, "rt_denoise: image size %dx%d (1 <= width height <= 2^31 - 1)", width, height);
+    if (!counts && samples < 1)
+        return fail(c, RT_ERR_INVALID, "rt_denoise: counts is NULL and samples is %d (>= 1)", samples);
+    const rt_aov_buffers g = guides ? *guides : rt_aov_buffers{nullptr, nullptr, nullptr, nullptr, nullptr};
+    if (g.albedo && (!g.hits || guide_samples < 1))
+        return fail(c, RT_ERR_INVALID, "rt_denoise: an albedo guide needs hits (%p) and guide_samples %d >= 1",
+                    (void*)g.hits, guide_samples);
+    const rt_denoise_params dp = params ? *params : DENOISE_DEFAULTS;
+    if (dp.iterations < 0 || dp.iterations > 8 || dp.normal_log2_power < 0 || dp.normal_log2_power > 10)
+        return fail(c, RT_ERR_INVALID, "rt_denoise: 0 <= iterations %d <= 8, 0 <= normal_log2_power %d <= 10",
+                    dp.iterations, dp.normal_log2_power);
+    if (!(std::isfinite(dp.sigma_depth) && dp.sigma_depth > 0.0 && std::isfinite(dp.sigma_lum) && dp.sigma_lum >= 0.0 &&
+          std::isfinite(dp.lum_eps) && dp.lum_eps > 0.0))
+        return fail(c, RT_ERR_INVALID, "rt_denoise: sigma_depth %g > 0, sigma_lum %g >= 0 and lum_eps %g > 0 must be finite",
+                    dp.sigma_depth, dp.sigma_lum, dp.lum_eps);
+    HIPCHK(c, hipSetDevice(c->device));
+    const size_t image = (size_t)width * (size_t)height * 4 * elem_bytes(c);
+    int rc;
+    if ((rc = reserve(c, c->d_dn_a, image)) || (rc = reserve(c, c->d_dn_b, dp.iterations ? image : 0)) ||
+        (rc = reserve(c, c->d_dn_guide, image)))
+        return rc;
+    hipStream_t st = stream_of(c, stream);
+    HIPCHK(c, hipEventRecord(c->ev0, st));
+    DenoiseLaunch D;
+    D.elem_bytes = (int)elem_bytes(c), D.width = width, D.height = height;
+    D.samples = samples, D.guide_samples = guide_samples;
+    D.iterations = dp.iterations, D.normal_log2_power = dp.normal_log2_power;
+    D.sigma_depth = dp.sigma_depth, D.sigma_lum = dp.sigma_lum, D.lum_eps = dp.lum_eps;
+    D.sums = sums, D.sumsq = sumsq, D.counts = counts;
+    D.albedo = g.albedo, D.normal = g.normal, D.depth = g.depth, D.hits = g.albedo ? g.hits : nullptr;
+    D.col_a = c->d_dn_a.p, D.col_b = c->d_dn_b.p, D.guide = c->d_dn_guide.p;
+    D.out = out, D.out_variance = out_variance;
+    return timed_end(c, st, launch_denoise(D, st), "denoise launch");
+}
+
 int rt_trace_rays_diag(rt_ctx* c, const void* rays, int n, rt_hit* hits, uint64_t counters[4]) {
     if (!c || !counters) return RT_ERR_INVALID;
     if (c->precision != RT_PREC_F32 || c->scene.n_mnodes > 0)

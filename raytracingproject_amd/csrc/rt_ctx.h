@@ -119,6 +119,9 @@ struct rt_ctx : rt_ctx_base {
     // from the environment's RT_AOV_COMBINE at rt_create
     DevBuf d_aov_near;
     int aov_combine = 1;
+    // rt_denoise (grown on demand): the two colour record images its passes ping-pong between and
+    // the guide record image, width x height x 4 values of the context precision each
+    DevBuf d_dn_a, d_dn_b, d_dn_guide;
     DevBuf d_gather;  // rt_render_frame_multi: all contexts' shards
 
     // fp32 fixed-point pixel sums (RenderParams::accum), one slot per output buffer the

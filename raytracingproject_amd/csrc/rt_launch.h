@@ -157,6 +157,21 @@ hipError_t launch_aov_reduce(const unsigned long long* offsets, int num_jobs, un
 hipError_t launch_refine_jobs(void* jobs, int num_jobs, const void* sums, const void* sumsq, int elem_bytes,
                               double rel_error, double abs_floor, uint32_t min_samples, uint32_t max_samples,
                               uint32_t max_step, unsigned long long* stats, hipStream_t stream);
+// rt_denoise (csrc/rt_denoise.h, rt_denoise.hip): prepare, `iterations` a-trous passes of step
+// 2^i that ping-pong between col_a and col_b, finish -- all on `stream`.  Images are width x
+// height of elem_bytes 4 or 8; sumsq, counts, albedo (with hits), normal, depth and out_variance
+// may be null; col_a, col_b, guide: scratch of width x height x 4 elements each, 4-element
+// aligned.  The parameters are rt_denoise_params', validated by the caller.
+struct DenoiseLaunch {
+    int elem_bytes, width, height, samples, guide_samples, iterations, normal_log2_power;
+    double sigma_depth, sigma_lum, lum_eps;
+    const void *sums, *sumsq;
+    const uint32_t* counts;
+    const void *albedo, *normal, *depth;
+    const uint32_t* hits;
+    void *col_a, *col_b, *guide, *out, *out_variance;
+};
+hipError_t launch_denoise(const DenoiseLaunch& D, hipStream_t stream);
 hipError_t launch_tape_f64(const RenderParams& P, int max_depth, const double* ray7, const double* tape, int tape_len,
                            double* out, int* used, hipStream_t stream);
 // element: 4 (float/uint32) or 8 (double); channels: 1 or 3
