@@ -779,8 +779,12 @@ int rt_render_diag(rt_ctx* ctx, const rt_camera* cam, int samples_per_pixel, int
  * 0 for every other kernel): the pop passes of slot 27 by the number of lanes that popped in
  * the pass -- 32: 1-2 lanes, 33: 3-6, 34: 7-16, 35: more than 16, for passes that do not
  * directly follow a batch in which a lane adopted its hit; 36-39: the same four buckets for
- * passes that directly follow such a batch in the same shade round.  The eight sum to slot 27. */
-enum { RT_DIAG_SLOTS = 40 };
+ * passes that directly follow such a batch in the same shade round.  The eight sum to slot 27.
+ * The same kernels, per shade pass of a wave (one trip of the shade loop: sky finishes, pops,
+ * one scatter pass): 30 shade passes, 40 those in which at least one lane flushed a finished
+ * sample straight to HBM (slot 25's samples), 41 those whose scatter pass held both a metal and a
+ * dielectric lane. */
+enum { RT_DIAG_SLOTS = 42 };
 int rt_render_diag_ex(rt_ctx* ctx, const rt_camera* cam, int samples_per_pixel, int max_depth, uint64_t* counters,
                       int n);
 

@@ -23,7 +23,7 @@ RT_TRAV_GRID = 65536   # fp32 sphere scenes: the uniform sphere grid (ABI 8)
 RT_TRAV_GFLAT, RT_TRAV_G3D = 131072, 262144   # its flat walk (added by the library), keep the 3-D walk (ABI 11)
 # (RT_TRAV_TBIN and RT_TRAV_MTOP: removed in ABI 6, refused by rt_set_tuning)
 RT_TRAV_DEFAULT = RT_TRAV_COH | RT_TRAV_SELROOT | RT_TRAV_B128 | RT_TRAV_CULL | RT_TRAV_GRID
-RT_DIAG_SLOTS = 40  # rt_hip.h: counters of rt_render_diag_ex
+RT_DIAG_SLOTS = 42  # rt_hip.h: counters of rt_render_diag_ex
 RT_COMM_ID_BYTES = 128
 RT_LAMBERTIAN, RT_METAL, RT_DIELECTRIC = 0, 1, 2
 RT_PREC_F32, RT_PREC_F64 = 0, 1
@@ -500,6 +500,11 @@ class Renderer:
         # then those that do
         hist = [int(c[k]) for k in range(32, 40)]
         d.update(pop_pass_hist=hist[:4] if grid else None, pop_pass_hist_after_adopt=hist[4:] if grid else None)
+        # slots 30, 40, 41, the same kernels, per shade pass of a wave (sky finishes, pops, one scatter
+        # pass): the passes, those in which a lane flushed a sample straight to HBM, those whose
+        # scatter pass held a metal and a dielectric lane
+        d.update(shade_passes=d["mtri_act"] if grid else None, direct_flush_passes=int(c[40]) if grid else None,
+                 metal_glass_passes=int(c[41]) if grid else None)
         return d
 
     def trace_rays(self, rays_dev: int, n: int, hits_dev: int, stream: int | None = None) -> None:

@@ -37,7 +37,7 @@ UNITS = {
     "rt_comm.cpp": [],
 }
 HEADERS = ["rt_device.h", "rt_render_impl.h", "rt_occluded.h", "rt_radiance.h", "rt_pixels.h", "rt_moments.h", "rt_aov.h", "rt_scene.h", "rt_launch.h", "rt_bvh.h", "rt_lbvh.h", "rt_ctx.h", "rt_devbuf.h",
-           "rt_treelet.h", "rt_pack.h", "rt_batch_cull.h", "rt_denoise.h"]
+           "rt_treelet.h", "rt_pack.h", "rt_batch_cull.h", "rt_denoise.h", "rt_quant.h"]
 
 
 def _stale(target: Path, deps: list[Path]) -> bool:
@@ -182,6 +182,24 @@ def build_devbuf(verbose: bool = False) -> Path:
     HIP's headers are used: no HIP library is linked, and no GPU code."""
     extra = ["-D__HIP_PLATFORM_AMD__", f"-I{CSRC}", "-I/opt/rocm/include"]
     return _build_san(DEVBUF_EXE, [ROOT / "tests" / "cpp" / "devbuf_driver.cpp"], [CSRC / "rt_devbuf.h"], extra, verbose)
+
+
+QUANT_EXE = OBJ / "san" / "quant_range_driver"
+
+
+def build_quant_range(verbose: bool = False) -> Path:
+    """tests/cpp/quant_range_driver.cpp (the finish path's range test of csrc/rt_quant.h and what a
+    finished sample adds to the frame, before and after the lean finish, over every bit pattern of
+    a channel; run by tests/test_quant_range.py).  Plain g++ -O2, no sanitizer: the driver owns no
+    memory and runs 2^33 samples.  No GPU code."""
+    src = ROOT / "tests" / "cpp" / "quant_range_driver.cpp"
+    QUANT_EXE.parent.mkdir(parents=True, exist_ok=True)
+    if _stale(QUANT_EXE, [src, CSRC / "rt_quant.h", CSRC / "rt_scene.h", Path(__file__)]):
+        cmd = ["g++", "-std=c++17", "-O2", "-Wall", "-pthread", f"-I{CSRC}", INC, str(src), "-o", str(QUANT_EXE)]
+        if verbose:
+            print(" ".join(cmd), flush=True)
+        subprocess.run(cmd, check=True)
+    return QUANT_EXE
 
 
 CULL_EXE = OBJ / "san" / "batch_cull_driver"

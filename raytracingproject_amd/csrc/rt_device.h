@@ -14,6 +14,7 @@
 
 #include "rt_scene.h"
 #include "rt_batch_cull.h"
+#include "rt_quant.h"
 
 
 namespace rtx {
@@ -240,7 +241,7 @@ __device__ __forceinline__ long long fix_sample(float l, int c, uint32_t& fl, fl
     fl |= (q != q ? FIX_NAN : q > 0 ? FIX_POS : FIX_NEG) << (3 * c);
     return 0;
 }
-constexpr int DIAG_SLOTS = 40;   // rt_render_diag_ex (RT_DIAG_SLOTS)
+constexpr int DIAG_SLOTS = 42;   // rt_render_diag_ex (RT_DIAG_SLOTS)
 
 // Coherent primaries (TRAV_COH, render_coherent): per wave, a FIFO of primary hits that
 // wait for a lane to shade them, then the current work item's pixel sums (64 x 3 floats).
@@ -284,6 +285,20 @@ static_assert(sizeof(CohEntryD<false>) == 16 && sizeof(CohEntryD<true>) == 24, "
 #endif
 #ifndef RT_CAM_ONEBASE
 #define RT_CAM_ONEBASE 1
+#endif
+// Compile-time switches of r18's three parts, the same way (DESIGN.md section 5 "Round 18"):
+// RT_LEAN_FINISH (render_coherent's finish: rt_quant.h's integer range test, a packed-word add
+// without flush_sample's per-channel tail for a sample in [0, 1] outside the item sums),
+// RT_SCATTER_PROLOGUE (scatter: one unit(din) / reflect for metal and glass),
+// RT_BATCH_ONEADOPT (the batch: one validity predicate, one block that adopts the hit)
+#ifndef RT_LEAN_FINISH
+#define RT_LEAN_FINISH 1
+#endif
+#ifndef RT_SCATTER_PROLOGUE
+#define RT_SCATTER_PROLOGUE 1
+#endif
+#ifndef RT_BATCH_ONEADOPT
+#define RT_BATCH_ONEADOPT 1
 #endif
 // r13, the fp32 sphere-grid kernels (coh_rng0): the entry also carries the path's RNG state
 // right after CounterRng::start, as the batch computed it, so that the pop sets it instead of
@@ -682,6 +697,14 @@ constexpr bool coh_adopts(bool mesh, int tr, bool f64) { return coh_cands(mesh, 
 // camera block is read through one LDS base (camera_ray_lds ONEBASE)
 constexpr bool coh_rng0(bool mesh, int tr, bool f64) { return RT_FIFO_RNG0 && coh_cands(mesh, tr, f64); }
 constexpr bool coh_cam1(bool mesh, int tr, bool f64) { return RT_CAM_ONEBASE && coh_cands(mesh, tr, f64); }
+// r18, the same kernels: the lean finish, scatter's shared reflect prologue, the batch's one adoption point
+constexpr bool coh_lean(bool mesh, int tr, bool f64) { return RT_LEAN_FINISH && coh_cands(mesh, tr, f64); }
+// (coh_refl1: the flat-walk kernels only.  With it and the one adoption point together the
+// allocator spills 9 VGPRs in the 3-D walk's kernel 66136, against 3 before and 2 without it)
+constexpr bool coh_refl1(bool mesh, int tr, bool f64) {
+    return RT_SCATTER_PROLOGUE && coh_cands(mesh, tr, f64) && (tr & TRAV_GFLAT) != 0;
+}
+constexpr bool coh_adopt1(bool mesh, int tr, bool f64) { return RT_BATCH_ONEADOPT && coh_cands(mesh, tr, f64); }
 // LDS views by 32-bit LDS byte address (the sphere grid's flat walk and record reads)
 typedef __attribute__((address_space(3))) const uint32_t lds_cu32;
 typedef __attribute__((address_space(3))) const float4 lds_cf4;
@@ -1455,9 +1478,47 @@ __device__ __forceinline__ V3<R> random_in_unit_sphere(Rng& rng) {
 }
 
 // material::scatter (material.h:15-82).  Returns false when absorbed.
-template <class R, bool EXACT, class Rng>
+// REFL1 (r18, the fp32 sphere-grid kernels): metal and glass both need reflect(unit(din), normal).
+// A wave that shades both ran the two copies back to back under complementary masks; here every
+// lane that is not lambertian computes it once, after the draw the metal lanes share with the
+// lambertian ones (no draw moves), and each material's tail picks it up: the same functions on
+// the same inputs, so the same bits.
+template <class R, bool EXACT, bool REFL1 = false, class Rng>
 __device__ __forceinline__ bool scatter(const typename Prec<R>::Mat& m, uint32_t type, const V3<R>& din,
                                         const Shade<R>& s, Rng& rng, V3<R>& att, V3<R>& dir) {
+    static_assert(!REFL1 || !EXACT, "REFL1: the fp32 kernels");
+    if constexpr (REFL1) {
+        V3<R> p = mk((R)0, (R)0, (R)0);
+        if (type != MAT_DIELECTRIC) p = random_in_unit_sphere<R>(rng);
+        if (type == MAT_LAMBERTIAN) {
+            att = mk((R)m.p[0], (R)m.p[1], (R)m.p[2]);
+            dir = s.normal + unit(p);
+            return true;
+        }
+        const V3<R> ud = unit(din);
+        const V3<R> rf = reflect(ud, s.normal);
+        if (type != MAT_DIELECTRIC) {
+            att = mk((R)m.p[0], (R)m.p[1], (R)m.p[2]);
+            dir = madd((R)m.p[3], p, rf);
+            return dot(dir, s.normal) > 0;
+        }
+        att = mk((R)1.0, (R)1.0, (R)1.0);
+        const R ir = (R)m.p[3];
+        const R ratio = s.front_face ? rcp(ir) : ir;
+        const R cos_theta = fmin(dot(-ud, s.normal), (R)1.0);
+        const R sin_theta = (R)sqrt((R)1.0 - cos_theta * cos_theta);
+        bool refl = ratio * sin_theta > (R)1.0;
+        if (!refl) {                                                   // short-circuit ||: no draw on TIR
+            R r0 = ((R)1 - ratio) / ((R)1 + ratio);
+            r0 = r0 * r0;
+            const R x = (R)1 - cos_theta;
+            const R x2 = x * x;
+            const R x5 = x2 * x2 * x;
+            refl = r0 + ((R)1 - r0) * x5 > rng.template next<R>();
+        }
+        dir = refl ? rf : refract(ud, s.normal, ratio);
+        return true;
+    }
     if (type != MAT_DIELECTRIC) {
         // lambertian (material.h:19-25) and metal (:35-41) both draw ONE
         // random_in_unit_sphere; drawing it on a shared path keeps the wave's rejection

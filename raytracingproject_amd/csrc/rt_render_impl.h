@@ -508,6 +508,11 @@ __device__ __forceinline__ void render_coherent(const RenderParams& P0, const Sc
     // a finished sample: into the current item's LDS sums, or straight to HBM
     // this lane's path: eligible for the LDS sums while its item is the wave's current one
     bool elig = false;
+    constexpr bool LEAN = coh_lean(MESH, TRAV, EXACT);   // r18 (rt_device.h RT_LEAN_FINISH)
+    // DIAG (r18): per shade pass, did a lane flush a sample straight to HBM; shade passes, those
+    // with such a flush, those whose scatter pass held a metal and a dielectric lane (wave-uniform)
+    [[maybe_unused]] bool direct_here = false;
+    [[maybe_unused]] unsigned long long n_shade_pass = 0, n_pass_direct = 0, n_pass_mixed = 0;
     auto finish = [&](uint32_t pp, bool in_item, V3<R> L, uint32_t sg, uint32_t srel) {
         if constexpr (EXACT) {
             R* o = samp + ((size_t)srel * npx_all + pp) * 3;
@@ -519,6 +524,34 @@ __device__ __forceinline__ void render_coherent(const RenderParams& P0, const Sc
         }
         const float qx = __builtin_rintf(L.x * SC) * ISC, qy = __builtin_rintf(L.y * SC) * ISC,
                     qz = __builtin_rintf(L.z * SC) * ISC;
+        if constexpr (LEAN) {
+            // r18: the range test on the bit patterns (rt_quant.h); a sample in [0, 1] that the
+            // item sums do not take adds its packed words itself -- flush_sample's first branch
+            // with cnt = 1, value for value, without the per-channel tail -- and only a sample
+            // outside [0, 1] (or with a -0.0 channel, which adds nothing either way) goes through
+            // flush_sample: no lane of the benchmark scene
+            if (rtx::in01(qx, qy, qz)) {
+                if (SUMS && in_item) {
+                    const uint32_t q = pp & 63u;
+                    if (qx != 0.f) atomicAdd(isum + q, qx);
+                    if (qy != 0.f) atomicAdd(isum + 64 + q, qy);
+                    if (qz != 0.f) atomicAdd(isum + 128 + q, qz);
+                    if (DIAG) ++n_in_item;
+                } else {
+                    const uint32_t ux = (uint32_t)(qx * SC), uy = (uint32_t)(qy * SC), uz = (uint32_t)(qz * SC);
+                    const unsigned long long prg = (unsigned long long)ux | (unsigned long long)uy << 32;
+                    if (prg) atomicAdd(P.accp + (size_t)pp * 2, prg);
+                    if (uz) atomicAdd(P.accp + (size_t)pp * 2 + 1, (unsigned long long)uz);
+                    if (DIAG) ++n_direct, direct_here = true;
+                }
+                if (P.out_segs && sg) atomicAdd(P.out_segs + pp, sg);
+            } else {
+                flush_sample(P, pp, qx, qy, qz, sg);
+                if (DIAG) ++n_direct, direct_here = true;
+            }
+            if (DIAG) ++n_paths;
+            return;
+        }
         const bool in01 = qx >= 0.f && qx <= 1.f && qy >= 0.f && qy <= 1.f && qz >= 0.f && qz <= 1.f;
         if (SUMS && in_item && in01) {
             const uint32_t q = pp & 63u;
@@ -529,7 +562,7 @@ __device__ __forceinline__ void render_coherent(const RenderParams& P0, const Sc
             if (DIAG) ++n_in_item;
         } else {
             flush_sample(P, pp, qx, qy, qz, sg);
-            if (DIAG) ++n_direct;
+            if (DIAG) ++n_direct, direct_here = true;
         }
         if (DIAG) ++n_paths;
     };
@@ -582,6 +615,7 @@ __device__ __forceinline__ void render_coherent(const RenderParams& P0, const Sc
     constexpr bool ADOPT = coh_adopts(MESH, TRAV, EXACT);
     // (the adoption sets thr and nsc in registers and no psid: not the parked state, not EXACT)
     static_assert(!ADOPT || (!PARK && !EXACT), "adopted hits: the fp32 sphere-only grid kernels");
+    constexpr bool ADOPT1 = ADOPT && coh_adopt1(MESH, TRAV, EXACT);   // r18 (rt_device.h RT_BATCH_ONEADOPT)
     [[maybe_unused]] unsigned long long n_adopt = 0, n_pop_pass = 0, n_pop_lanes = 0;   // DIAG
     // DIAG (r13): pop passes by the lanes that pop in them (1-2, 3-6, 7-16, more), those that
     // directly follow a batch in which a lane adopted (the same pop loop) counted apart
@@ -634,7 +668,11 @@ __device__ __forceinline__ void render_coherent(const RenderParams& P0, const Sc
             }
         }
         const int s = cur.s0 + bi++;
-        const int px = cur.tx0 + (lane & 7), py = cur.ty0 + (lane >> 3);
+        // (ADOPT1: lane & 7 and lane >> 3 from an opaque copy of the lane, one VALU each per batch;
+        // hoisted out of the rounds they were held in scratch and read back here)
+        int bl = lane;
+        if constexpr (ADOPT1) asm volatile("" : "+v"(bl));
+        const int px = cur.tx0 + (bl & 7), py = cur.ty0 + (bl >> 3);
         const uint32_t pp = (uint32_t)cur.lt * 64u + (uint32_t)lane;
         bool hit = false;
         [[maybe_unused]] bool adopt = false;
@@ -643,7 +681,49 @@ __device__ __forceinline__ void render_coherent(const RenderParams& P0, const Sc
         hb.id = -1;
         [[maybe_unused]] int kd = 15;
         [[maybe_unused]] uint32_t rng0 = 0;   // RNG0: the path's RNG state after start(), for its FIFO entry
-        if (px < P.W && py < P.H && P.max_depth > 0) {
+        if constexpr (ADOPT1) {
+            // r18: the same steps under one predicate each instead of nested -- the camera ray and
+            // its trace under `valid`, the sky finish where control has rejoined, and ONE block
+            // that writes the adopted path's state, so that the lane's path registers are merged
+            // once and not on every exit of three nested conditions.  Per lane the operations and
+            // their operands are those of the nested form below.
+            const bool valid = px < P.W && py < P.H && P.max_depth > 0;
+            Ray<R> pr;   // (read under `valid` only)
+            [[maybe_unused]] CounterRng r2;
+            if (valid) {
+                r2.start(hash32(P.seed32 ^ (uint32_t)(py * P.W + px)), (uint32_t)s);
+                if constexpr (RNG0) rng0 = r2.st;
+                pr = KDEF ? cam_ray(px, py, r2, -1, &kd) : cam_ray(px, py, r2);
+                const int nc = __builtin_amdgcn_readfirstlane((int)clist[BATCH_CAND_CAP]);
+                if (nc >= 0)
+                    hb = closest_hit<R, EXACT, DIAG, TR, MESH, false, true>(sc, pr, stack, BLOCK, NO_SELF, &dgb, nullptr,
+                                                                            nullptr, 0, 0, (uint32_t)(uintptr_t)clist, nc);
+                else
+                    hb = closest_hit<R, EXACT, DIAG, TR, MESH>(sc, pr, stack, BLOCK, NO_SELF, &dgb);
+            }
+            hit = hb.id != -1;   // (hb.id stays -1 without a trace)
+            if (valid && !hit) finish(pp, true, sky(pr.d), 1u, (uint32_t)(s - P.sample_begin));
+            adopt = hit && need && P.batch_adopt;
+            if (adopt) {
+                ray = pr;
+                if constexpr (RNG0) {
+                    rng.st = rng0;   // (the state after the camera ray's draws: see the nested form)
+                    rng.skip(3u + (P.defocus ? 2u * (uint32_t)kd + 2u : 0u));
+                } else {
+                    rng = r2;
+                }
+                h.t = hb.t;
+                h.td = (double)hb.t;
+                h.id = hb.id;
+                pix = pp;
+                thr = mk((R)1, (R)1, (R)1);
+                nsc = 0;
+                self = NO_SELF;
+                live = ready = true;
+                elig = true;
+                if (DIAG) ++n_adopt;
+            }
+        } else if (px < P.W && py < P.H && P.max_depth > 0) {
             CounterRng r2;
             r2.start(hash32(P.seed32 ^ (uint32_t)(py * P.W + px)), (uint32_t)s);
             if constexpr (RNG0) rng0 = r2.st;
@@ -825,8 +905,14 @@ __device__ __forceinline__ void render_coherent(const RenderParams& P0, const Sc
                 bool done = true;
                 const Shade<R> sh = shade<R, MESH>(sc, ray, h);
                 V3<R> att, dir;
-                if (scatter<R, EXACT>(sc.mat[sh.meta & META_MAT_MASK], (sh.meta >> 24) & 3u, ray.d, sh, rng, att,
-                                      dir)) {
+                if constexpr (DIAG && CAND) {   // (slot 41)
+                    const uint32_t ty = (sh.meta >> 24) & 3u;
+                    if (__ballot(ty == MAT_DIELECTRIC) != 0 && __ballot(ty != MAT_DIELECTRIC && ty != MAT_LAMBERTIAN) != 0 &&
+                        lane == __builtin_ctzll(__builtin_amdgcn_read_exec()))
+                        ++n_pass_mixed;
+                }
+                if (scatter<R, EXACT, coh_refl1(MESH, TRAV, EXACT)>(sc.mat[sh.meta & META_MAT_MASK], (sh.meta >> 24) & 3u,
+                                                                    ray.d, sh, rng, att, dir)) {
                     if constexpr (PARK) {
                         nsc = park_nsc();
                         park_set(park_thr() * att, nsc + 1);
@@ -848,6 +934,14 @@ __device__ __forceinline__ void render_coherent(const RenderParams& P0, const Sc
                     if constexpr (PARK) nsc = park_nsc();
                     finish(pix, elig, mk((R)0, (R)0, (R)0), (uint32_t)nsc + (nsc >= P.max_depth ? 0u : 1u), psid);
                     live = false;
+                }
+            }
+            if constexpr (DIAG && CAND) {   // (slots 30 and 40)
+                const bool any_direct = __ballot(direct_here) != 0;
+                direct_here = false;
+                if (lane == 0) {
+                    ++n_shade_pass;
+                    n_pass_direct += any_direct ? 1u : 0u;
                 }
             }
             // another round only while enough lanes hold no ray (a round costs the whole wave;
@@ -903,6 +997,9 @@ __device__ __forceinline__ void render_coherent(const RenderParams& P0, const Sc
             if (l0 && n_pop_pass) atomicAdd(P.diag + 27, n_pop_pass);
             if (l0 && n_pop_lanes) atomicAdd(P.diag + 28, n_pop_lanes);
             if (n_adopt) atomicAdd(P.diag + 29, n_adopt);
+            if (n_shade_pass) atomicAdd(P.diag + 30, n_shade_pass);
+            if (n_pass_direct) atomicAdd(P.diag + 40, n_pass_direct);
+            if (n_pass_mixed) atomicAdd(P.diag + 41, n_pass_mixed);
             for (int j = 0; j < 8; ++j)   // 32-39: the pop passes of slot 27 by lane count
                 if (l0 && n_pass_hist[j]) atomicAdd(P.diag + 32 + j, n_pass_hist[j]);
         }

@@ -127,6 +127,14 @@ def main():
                     for b, x, y in zip(["1-2", "3-6", "7-16", "17-64"], d["pop_pass_hist"], d["pop_pass_hist_after_adopt"])
                 },
             }
+            # r18 (slots 30, 40, 41): per shade pass of a wave, how often the finish path's direct
+            # flush and scatter's two reflecting materials are met
+            out["round_paths"] = {
+                "shade_passes": d["shade_passes"], "shade_passes_per_bounce_iter": q(d["shade_passes"], d["bounce_it"]),
+                "direct_flush_pass_share": q(d["direct_flush_passes"], d["shade_passes"]),
+                "metal_glass_pass_share": q(d["metal_glass_passes"], d["shade_passes"]),
+                "batches": d["k_it1"], "bounce_iters": d["bounce_it"],
+            }
         if mesh:
             traced = rays + d["segments"]   # camera rays (batches) + scattered rays
             out["mesh"] = {

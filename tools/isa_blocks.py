@@ -6,7 +6,8 @@ Used to count straight-line paths that tools/isa_loops.py does not look for (it 
 traversal loops), such as render_coherent's pop: the only code of the fp32 sphere-grid kernels
 with an fp64 FMA (the tile-row decode) and a run of v_mul_lo_u32 (the three hash32 of rng.start).
 
-python tools/isa_blocks.py FILE.s KERNEL_SUBSTRING [--has REGEX]     (--has . : every block)
+python tools/isa_blocks.py FILE.s KERNEL_SUBSTRING [--has REGEX] [--min-moves N]     (--has . : every block)
+(--min-moves N: only blocks with at least N v_mov_b32 / v_mov_b64, the runs of register copies)
 (FILE.s: hipcc -S --cuda-device-only with build.py's flags; a line reads
  "block INDEX LABEL-or-%bb-number: counts")
 """
@@ -19,6 +20,7 @@ def main():
     ap.add_argument("asm")
     ap.add_argument("kernel")
     ap.add_argument("--has", default=r"v_fma_f64|v_mul_lo_u32")
+    ap.add_argument("--min-moves", type=int, default=0)
     a = ap.parse_args()
     lines = open(a.asm).read().splitlines()
     start = next(i for i, l in enumerate(lines) if re.match(r"^_Z\w+:", l) and a.kernel in l)
@@ -36,7 +38,7 @@ def main():
             cur["ins"].append(t)
 
     def mix(ins):
-        c = dict(valu=0, imul=0, f64=0, salu=0, lds=0, smem=0, readlane=0, vmem=0, branch=0)
+        c = dict(valu=0, imul=0, f64=0, salu=0, lds=0, smem=0, readlane=0, vmem=0, branch=0, mov=0)
         for t in ins:
             op = t.split()[0]
             if op.startswith(("v_readlane", "v_readfirstlane", "v_writelane")):
@@ -46,6 +48,7 @@ def main():
                 c["valu"] += 1
                 c["imul"] += op.startswith(("v_mul_lo_u32", "v_mul_hi_u32", "v_mad_u64_u32", "v_mul_lo_i32"))
                 c["f64"] += "f64" in op
+                c["mov"] += op.startswith(("v_mov_b32", "v_mov_b64"))
             elif op.startswith(("s_load", "s_buffer_load")):
                 c["smem"] += 1
             elif op.startswith(("s_cbranch", "s_branch")):
@@ -63,6 +66,8 @@ def main():
         if not any(re.search(a.has, t) for t in b["ins"]):
             continue
         c = mix(b["ins"])
+        if c["mov"] < a.min_moves:
+            continue
         print(f"block {k} {b['name']}: " + " ".join(f"{n}={v}" for n, v in c.items()))
         tot = c if tot is None else {n: tot[n] + c[n] for n in c}
     if tot:
