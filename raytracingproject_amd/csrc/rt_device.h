@@ -300,6 +300,12 @@ static_assert(sizeof(CohEntryD<false>) == 16 && sizeof(CohEntryD<true>) == 24, "
 #ifndef RT_BATCH_ONEADOPT
 #define RT_BATCH_ONEADOPT 1
 #endif
+// Compile-time switch of r19, the same way (DESIGN.md section 5 "Round 19"; at 0 the kernels are
+// r18's, instruction for instruction): RT_POP_THROUGH (render_coherent's pop loop: after a batch
+// the loop's head tests are made in place and the pop follows without a turn of the loop)
+#ifndef RT_POP_THROUGH
+#define RT_POP_THROUGH 1
+#endif
 // r13, the fp32 sphere-grid kernels (coh_rng0): the entry also carries the path's RNG state
 // right after CounterRng::start, as the batch computed it, so that the pop sets it instead of
 // hashing pixel and sample again.  One 16-byte LDS write and one 16-byte LDS read per entry.
@@ -705,6 +711,8 @@ constexpr bool coh_refl1(bool mesh, int tr, bool f64) {
     return RT_SCATTER_PROLOGUE && coh_cands(mesh, tr, f64) && (tr & TRAV_GFLAT) != 0;
 }
 constexpr bool coh_adopt1(bool mesh, int tr, bool f64) { return RT_BATCH_ONEADOPT && coh_cands(mesh, tr, f64); }
+// r19, the same kernels: the pop follows its batch inside one turn of the pop loop
+constexpr bool coh_popthru(bool mesh, int tr, bool f64) { return RT_POP_THROUGH && coh_cands(mesh, tr, f64); }
 // LDS views by 32-bit LDS byte address (the sphere grid's flat walk and record reads)
 typedef __attribute__((address_space(3))) const uint32_t lds_cu32;
 typedef __attribute__((address_space(3))) const float4 lds_cf4;

@@ -616,6 +616,7 @@ __device__ __forceinline__ void render_coherent(const RenderParams& P0, const Sc
     // (the adoption sets thr and nsc in registers and no psid: not the parked state, not EXACT)
     static_assert(!ADOPT || (!PARK && !EXACT), "adopted hits: the fp32 sphere-only grid kernels");
     constexpr bool ADOPT1 = ADOPT && coh_adopt1(MESH, TRAV, EXACT);   // r18 (rt_device.h RT_BATCH_ONEADOPT)
+    constexpr bool POP_THRU = ADOPT1 && coh_popthru(MESH, TRAV, EXACT);   // r19 (rt_device.h RT_POP_THROUGH)
     [[maybe_unused]] unsigned long long n_adopt = 0, n_pop_pass = 0, n_pop_lanes = 0;   // DIAG
     // DIAG (r13): pop passes by the lanes that pop in them (1-2, 3-6, 7-16, more), those that
     // directly follow a batch in which a lane adopted (the same pop loop) counted apart
@@ -833,16 +834,23 @@ __device__ __forceinline__ void render_coherent(const RenderParams& P0, const Sc
             }
             // lanes without a path pop a primary hit (batches refill the FIFO)
             for (;;) {
-                const bool need = !fin && !live;
-                const unsigned long long m = __ballot(need);
+                bool need = !fin && !live;
+                unsigned long long m = __ballot(need);
                 if (m == 0) break;
-                const uint32_t k = (uint32_t)__popcll(m);
+                uint32_t k = (uint32_t)__popcll(m);
                 // a batch appends up to 64 hits: it runs when the FIFO has room for them
                 // (always, at 128 entries: count < k <= 64); otherwise the hits already
                 // there are popped first and the lanes still waiting batch next time round
                 if (count < k && !dry && count + 64u <= (uint32_t)FIFO) {
                     batch(need);
-                    continue;
+                    if constexpr (!POP_THRU) continue;
+                    // r19: the same tests as the loop's head, made here, so that the pop of the
+                    // lanes that adopted nothing follows its batch without a turn of the loop
+                    need = !fin && !live;
+                    m = __ballot(need);
+                    if (m == 0) break;
+                    k = (uint32_t)__popcll(m);
+                    if (count < k && !dry && count + 64u <= (uint32_t)FIFO) continue;
                 }
                 if (need) {
                     const uint32_t r =

@@ -7,7 +7,10 @@ traversal loops), such as render_coherent's pop: the only code of the fp32 spher
 with an fp64 FMA (the tile-row decode) and a run of v_mul_lo_u32 (the three hash32 of rng.start).
 
 python tools/isa_blocks.py FILE.s KERNEL_SUBSTRING [--has REGEX] [--min-moves N]     (--has . : every block)
-(--min-moves N: only blocks with at least N v_mov_b32 / v_mov_b64, the runs of register copies)
+(--min-moves N: only blocks with at least N v_mov_b32 / v_mov_b64, the runs of register copies;
+ each such block is printed with its loop depth, and one closing line gives the share of v_mov
+ among the VALU of all blocks at depth >= 2 -- depth 1 is the kernel's straight-line code and
+ every enclosing natural loop adds one, so depth >= 2 is the round loop and all it holds)
 (FILE.s: hipcc -S --cuda-device-only with build.py's flags; a line reads
  "block INDEX LABEL-or-%bb-number: counts")
 """
@@ -37,6 +40,44 @@ def main():
         if t and not t.startswith(".") and not t.endswith(":"):
             cur["ins"].append(t)
 
+    def depths():
+        """1 + the number of natural loops (merged per header) around each block."""
+        idx = {b["name"]: i for i, b in enumerate(blocks)}
+        n = len(blocks)
+        succ = [set() for _ in range(n)]
+        for i, b in enumerate(blocks):
+            for t in b["ins"]:
+                m = re.match(r"s_(?:cbranch_\w+|branch)\s+(\.LBB\d+_\d+)", t)
+                if m and m.group(1) in idx:
+                    succ[i].add(idx[m.group(1)])
+            last = b["ins"][-1] if b["ins"] else ""
+            if not last.startswith(("s_branch", "s_endpgm")) and i + 1 < n:
+                succ[i].add(i + 1)
+        pred = [set() for _ in range(n)]
+        for i, ss in enumerate(succ):
+            for j in ss:
+                pred[j].add(i)
+        dom = [set(range(n)) for _ in range(n)]
+        dom[0] = {0}
+        changed = True
+        while changed:
+            changed = False
+            for i in range(1, n):
+                d = (set.intersection(*(dom[q] for q in pred[i])) if pred[i] else set()) | {i}
+                if d != dom[i]:
+                    dom[i], changed = d, True
+        loops = {}
+        for x in range(n):
+            for q in pred[x]:
+                if x in dom[q]:   # back edge q -> x
+                    body, work = loops.setdefault(x, {x}), [q]
+                    while work:
+                        w = work.pop()
+                        if w not in body:
+                            body.add(w)
+                            work.extend(pred[w])
+        return [1 + sum(i in body for body in loops.values()) for i in range(n)]
+
     def mix(ins):
         c = dict(valu=0, imul=0, f64=0, salu=0, lds=0, smem=0, readlane=0, vmem=0, branch=0, mov=0)
         for t in ins:
@@ -62,16 +103,22 @@ def main():
         return c
 
     tot = None
+    depth = depths() if a.min_moves else None
     for k, b in enumerate(blocks):
         if not any(re.search(a.has, t) for t in b["ins"]):
             continue
         c = mix(b["ins"])
         if c["mov"] < a.min_moves:
             continue
-        print(f"block {k} {b['name']}: " + " ".join(f"{n}={v}" for n, v in c.items()))
+        print(f"block {k} {b['name']}: " + " ".join(f"{n}={v}" for n, v in c.items()) +
+              (f" depth={depth[k]}" if depth else ""))
         tot = c if tot is None else {n: tot[n] + c[n] for n in c}
     if tot:
         print("sum: " + " ".join(f"{n}={v}" for n, v in tot.items()))
+    if depth:
+        inner = [mix(b["ins"]) for k, b in enumerate(blocks) if depth[k] >= 2]
+        valu, mov = sum(c["valu"] for c in inner), sum(c["mov"] for c in inner)
+        print(f"depth >= 2: {len(inner)} blocks, v_mov {mov} of {valu} VALU ({mov / max(1, valu):.1%})")
 
 
 if __name__ == "__main__":
