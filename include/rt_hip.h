@@ -269,6 +269,39 @@ int rt_upload_scene(rt_ctx* ctx, const rt_sphere* spheres, int num_spheres, cons
  * spheres, triangles and the big spheres that refract or move, and the parts of static opaque
  * big spheres visible from those).  Either way the same frame. */
 int rt_grid_reach(rt_ctx* ctx, const rt_camera* cam, int32_t* walks);
+/* What a job-list query runs for this camera on the current scene and tuning: rt_pixels_plan for
+ * rt_render_pixels, rt_pixels_plan_call for the call named by `call` (RT_QUERY_PIXELS
+ * rt_render_pixels, RT_QUERY_MOMENTS rt_render_pixels_moments, RT_QUERY_AOV rt_render_pixels_aov).
+ * The plan is per call family because the measurement was: a call walks the sphere grid only
+ * where the grid beat the tree by more than the two runs' spreads at every sample count measured
+ * (DESIGN.md §5 "Queries over the sphere grid") -- rt_render_pixels in both precisions and
+ * rt_render_pixels_moments in fp64 contexts.  rt_render_pixels_moments in fp32 contexts and
+ * rt_render_pixels_aov always walk the sphere tree (walks_grid 0).  A call that may walk the grid
+ * does so if and only if all of these hold: the scene has no triangle mesh; rt_upload_scene built a grid
+ * (rt_scene_info.grid_res != 0 0 0); rt_tuning.traversal carries 65536 (RT_TRAV_GRID), read at the
+ * call as rt_render reads it; in fp64 contexts rt_tuning.f64_kernel resolves to a grid kernel (0
+ * or 5; 3 and 4 force the tree, as for frames); the camera is within the walk's reach
+ * (rt_grid_reach); and the grid's layout fits 160 KiB of LDS at the queries' workgroup size.
+ * Otherwise they walk the sphere tree -- also where only the grid's layout does not fit.  The walk
+ * is the flat one (131072, x and z steps only) iff the grid is one cell tall in y and the
+ * traversal does not carry 262144 (RT_TRAV_G3D).  Either way the same outputs, bit for bit: the
+ * grid and the tree find the same hit.
+ * The per-ray queries (rt_trace_rays, rt_trace_rays_from, rt_occluded, rt_radiance_rays) take
+ * the caller's rays, for which there is no reach to prove, and always walk the tree.
+ * Launches nothing.  Errors: RT_ERR_INVALID for a NULL argument, a bad camera or an unknown call, RT_ERR_NO_SCENE
+ * before an upload, RT_ERR_LIMIT where the query itself would return it (neither layout fits the
+ * LDS, an image too large).  Added to ABI 12 without a version bump, as rt_occluded was. */
+typedef struct {
+    int32_t walks_grid;   /* 1: the sphere grid; 0: the sphere tree */
+    int32_t traversal;    /* the kernel's traversal flags (RT_TRAV_*: 536 for fp32 sphere trees, 8712 with
+                             a mesh, + 65536 [+ 131072] over the grid; fp64: 32 + the grid's flags, or 0
+                             for the tree) */
+    int32_t block;        /* threads per workgroup */
+    int32_t lds_bytes;    /* dynamic LDS per workgroup */
+} rt_pixels_plan_info;
+enum { RT_QUERY_PIXELS = 0, RT_QUERY_MOMENTS = 1, RT_QUERY_AOV = 2 };
+int rt_pixels_plan(rt_ctx* ctx, const rt_camera* cam, rt_pixels_plan_info* info);
+int rt_pixels_plan_call(rt_ctx* ctx, const rt_camera* cam, int call, rt_pixels_plan_info* info);
 int rt_scene_info_get(rt_ctx* ctx, rt_scene_info* info);
 /* Spheres plus triangles (configs 4/5: mesh, mixed).  Triangles get their own 4-wide BVH,
  * HBM-resident (nodes and triangles are read through L2/Infinity Cache with global loads;
@@ -512,7 +545,9 @@ int rt_radiance_rays(rt_ctx* ctx, const void* rays, int num_rays, const rt_path_
  * scattered segments only).  Out-of-range radiance aside, a job {p, s, n} is
  * rt_render_range(s, n) at pixel p bit for bit.
  * out_segments is overwritten, or added to with accumulate = 1.
- * The tree is walked, never the sphere grid (as for every query).  fp64 passes: each sample is
+ * The sphere grid is walked where rt_render would walk it for this camera, else the sphere tree
+ * (rt_pixels_plan says which, and when; rt_render_pixels_moments: rt_pixels_plan_call, the grid in
+ * fp64 contexts only); the sums are the same bits either way.  fp64 passes: each sample is
  * stored as a 28-byte record (3 doubles and one uint32) before the ordered reduction, and one
  * pass holds floor(rt_tuning.sample_buffer_mb 2^20 / 28) samples of the flat list; a job that
  * straddles a pass boundary continues in the next pass.
@@ -584,7 +619,7 @@ int rt_render_pixels_moments(rt_ctx* ctx, const rt_camera* cam, const rt_pixel_j
  * asynchronous on `stream` (NULL: the context's); rt_last_kernel_ms times it.
  * Not done here: compacting the job list (converged slots stay, at 16 bytes and one scan element
  * each), a fused finish kernel for a non-uniform n (divide sums by n yourself; rt_quantize(mean,
- * spp = 1) quantises), walking the sphere grid from queries, any use from rt_render.
+ * spp = 1) quantises), any use from rt_render.
  * Added to ABI 12 without a version bump. */
 typedef struct {
     double rel_error, abs_floor;
@@ -617,7 +652,10 @@ int rt_camera_rays(rt_ctx* ctx, const rt_camera* cam, const rt_pixel_job* jobs, 
  * Only the first segment is traced (there is no max_depth), and no RNG draw is spent beyond
  * get_ray's.
  * Per sample, r is the camera ray rt_camera_rays writes for it and h the rt_hit rt_trace_rays
- * returns for r: the tree, the same traversal flags, no origin id -- the same bits.
+ * returns for r: the tree, the same traversal flags, no origin id -- the same bits.  (Over the
+ * sphere grid the record is the same too -- tests/test_query_grid.py held a grid build of this
+ * call to it -- but the grid was not faster here, so the call keeps the tree:
+ * rt_pixels_plan_call(RT_QUERY_AOV).)
  * out: host struct of device pointers, each num_jobs records; a NULL member is skipped.
  *   hits    the number of the job's samples with h.id != -1; overwritten, or added to with
  *           accumulate = 1.  hits / sample_count is the coverage (1 - sky).
@@ -655,7 +693,8 @@ int rt_camera_rays(rt_ctx* ctx, const rt_camera* cam, const rt_pixel_job* jobs, 
  * num_jobs < 0 or a NULL jobs with num_jobs > 0; RT_ERR_LIMIT past 160 KiB of LDS or T > 2^31 - 1),
  * and RT_ERR_INVALID for a NULL out with num_jobs > 0 or an out whose five members are all NULL.
  * num_jobs == 0 is a no-op.  Shares rt_render_pixels' device scratch: same stream, or ordered.
- * Not done here: walking the sphere grid or coherent per-tile batches (queries walk the tree); a
+ * Not done here: coherent per-tile batches of the camera rays; the sphere grid (built and
+ * measured: 1.09x the tree's time in fp32, within the spreads in fp64 at 2 spp, so not kept); a
  * sky-coloured albedo for misses (blend with the coverage yourself).
  * Added to ABI 12 without a version bump, as rt_occluded. */
 typedef struct {

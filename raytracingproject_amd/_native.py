@@ -19,6 +19,7 @@ RT_ABI_VERSION = 12
 RT_TRAV_SELROOT, RT_TRAV_B128, RT_TRAV_COH = 8, 16, 64   # rt_hip.h traversal flags
 RT_TRAV_NOSUM, RT_TRAV_TBIN, RT_TRAV_CULL, RT_TRAV_MTOP, RT_TRAV_MIFIF, RT_TRAV_MWHILE = 128, 256, 512, 4096, 8192, 16384
 RT_TRAV_MQ = 32768
+RT_QUERY_PIXELS, RT_QUERY_MOMENTS, RT_QUERY_AOV = 0, 1, 2   # rt_pixels_plan_call's call
 RT_TRAV_GRID = 65536   # fp32 sphere scenes: the uniform sphere grid (ABI 8)
 RT_TRAV_GFLAT, RT_TRAV_G3D = 131072, 262144   # its flat walk (added by the library), keep the 3-D walk (ABI 11)
 # (RT_TRAV_TBIN and RT_TRAV_MTOP: removed in ABI 6, refused by rt_set_tuning)
@@ -67,6 +68,11 @@ class RtSceneInfo(C.Structure):
         [("grid_res", C.c_int32 * 3), ("grid_entries", C.c_int32),
          # ABI 10: the grid's build parameters and its walk's reach (rt_hip.h)
          ("grid_time_slabs", C.c_int32), ("grid_far_o", C.c_float), ("grid_density", C.c_double)]
+
+
+class RtPixelsPlanInfo(C.Structure):
+    """rt_pixels_plan_info (16 B): what a job-list query runs for a camera (rt_hip.h)."""
+    _fields_ = [(n, C.c_int32) for n in ("walks_grid", "traversal", "block", "lds_bytes")]
 
 
 class RtObjMesh(C.Structure):
@@ -120,6 +126,8 @@ SIGNATURES = {
     "rt_upload_scene": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int]),
     "rt_scene_info_get": (C.c_int, [C.c_void_p, C.POINTER(RtSceneInfo)]),
     "rt_grid_reach": (C.c_int, [C.c_void_p, C.POINTER(RtCamera), C.POINTER(C.c_int32)]),   # ABI 10
+    "rt_pixels_plan": (C.c_int, [C.c_void_p, C.POINTER(RtCamera), C.POINTER(RtPixelsPlanInfo)]),   # ABI 12
+    "rt_pixels_plan_call": (C.c_int, [C.c_void_p, C.POINTER(RtCamera), C.c_int, C.POINTER(RtPixelsPlanInfo)]),
     "rt_upload_scene_ex": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int]),
     "rt_obj_load": (C.c_int, [C.c_char_p, C.POINTER(RtObjMesh)]),
     "rt_obj_free": (None, [C.POINTER(RtObjMesh)]),
@@ -390,6 +398,18 @@ class Renderer:
         w = C.c_int32()
         self._check(self._L.rt_grid_reach(self.ctx, C.byref(cam), C.byref(w)), "rt_grid_reach")
         return bool(w.value)
+
+    def pixels_plan(self, cam: RtCamera, call: int = RT_QUERY_PIXELS) -> RtPixelsPlanInfo:
+        """rt_pixels_plan / rt_pixels_plan_call: what render_pixels (call RT_QUERY_PIXELS, the default),
+        render_pixels_moments (RT_QUERY_MOMENTS) or render_pixels_aov (RT_QUERY_AOV) runs for this
+        camera now -- the sphere grid or the sphere tree, the kernel's traversal flags, its workgroup
+        size and its LDS.  Launches nothing."""
+        info = RtPixelsPlanInfo()
+        if call == RT_QUERY_PIXELS:
+            self._check(self._L.rt_pixels_plan(self.ctx, C.byref(cam), C.byref(info)), "rt_pixels_plan")
+        else:
+            self._check(self._L.rt_pixels_plan_call(self.ctx, C.byref(cam), call, C.byref(info)), "rt_pixels_plan_call")
+        return info
 
     def render_frame(self, cam: RtCamera, spp: int, max_depth: int, want_segments: bool = True):
         """Whole frame, host outputs: (sums[H,W,3], rgb int32[H,W,3], segments uint32[H,W])."""

@@ -22,9 +22,12 @@ HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 
 COMMON = ["-x", "hip", f"--offload-arch={ARCH}", "-O3", "-std=c++17", "-fPIC", "-Wall",
           "-Wno-unused-function", f"-I{ROOT / 'include'}"] + os.environ.get("RT_HIPCC_EXTRA", "").split()
+F32_FAST = ["-fno-hip-fp32-correctly-rounded-divide-sqrt", "-fgpu-flush-denormals-to-zero",
+            os.environ.get("RT_F32_CONTRACT", "-ffp-contract=on")]
 UNITS = {
-    "rt_render_f32.hip": ["-fno-hip-fp32-correctly-rounded-divide-sqrt", "-fgpu-flush-denormals-to-zero",
-                          os.environ.get("RT_F32_CONTRACT", "-ffp-contract=on")],
+    "rt_render_f32.hip": F32_FAST,
+    # the fp32 job-list query kernels over the sphere grid: rt_render_f32.hip's flags, so its arithmetic
+    "rt_query_grid_f32.hip": F32_FAST,
     "rt_render_f64.hip": ["-ffp-contract=off"],
     "rt_abi.cpp": ["-ffp-contract=off"],
     "rt_plan.cpp": ["-ffp-contract=off"],

@@ -558,6 +558,28 @@ int rt_grid_reach(rt_ctx* c, const rt_camera* cam, int32_t* walks) {
     return RT_OK;
 }
 
+int rt_pixels_plan(rt_ctx* c, const rt_camera* cam, rt_pixels_plan_info* info) {
+    return rt_pixels_plan_call(c, cam, RT_QUERY_PIXELS, info);
+}
+
+int rt_pixels_plan_call(rt_ctx* c, const rt_camera* cam, int call, rt_pixels_plan_info* info) {
+    if (!c || !info) return RT_ERR_INVALID;
+    if (!cam) return fail(c, RT_ERR_INVALID, "camera is NULL");
+    if (call != RT_QUERY_PIXELS && call != RT_QUERY_MOMENTS && call != RT_QUERY_AOV)
+        return fail(c, RT_ERR_INVALID, "rt_pixels_plan_call: call %d (RT_QUERY_PIXELS, _MOMENTS or _AOV)", call);
+    if (!c->scene.has_scene) return fail(c, RT_ERR_NO_SCENE, "rt_pixels_plan before rt_upload_scene");
+    int rc = check_camera(c, cam);
+    if (rc) return rc;
+    const QueryPlan q = plan_job_query(c, call, grid_in_reach(c, cam));
+    if (q.lds_bytes > 160 * 1024)
+        return fail(c, RT_ERR_LIMIT, "rt_pixels_plan: a query needs %zu B of LDS per workgroup", q.lds_bytes);
+    info->walks_grid = q.grid ? 1 : 0;
+    info->traversal = q.trav;
+    info->block = q.block;
+    info->lds_bytes = (int32_t)q.lds_bytes;
+    return RT_OK;
+}
+
 int rt_shard_layout(int width, int height, int shard, int num_shards, rt_shard_info* info) {
     if (!info || width <= 0 || height <= 0 || num_shards <= 0 || shard < 0 || shard >= num_shards)
         return RT_ERR_INVALID;
@@ -980,16 +1002,23 @@ int rt_render_frame_multi(rt_ctx** cs, int n, const rt_camera* cam, int spp, int
     return RT_OK;
 }
 
-// The per-ray query launches (rt_trace_rays*, rt_occluded): the scene's tree in LDS at
-// TRACE_BLOCK threads, and its size there with the mesh stack's LDS columns.  view: the camera
-// of a query that makes its own rays (rt_render_pixels), else none.
-static int query_setup(rt_ctx* c, const char* what, RenderParams& P, size_t& lds, const rt_camera* view = nullptr) {
+// The query launches: the scene in LDS at TRACE_BLOCK threads, and its size there with the mesh
+// stack's LDS columns.  The per-ray queries (rt_trace_rays*, rt_occluded, rt_radiance_rays) take
+// the caller's rays and walk the tree.  view: the camera of a query that makes its own rays (the
+// job-list queries; call: which, RT_QUERY_*), which walks what plan_job_query says for it -- *grid
+// receives that plan's flags (0: the tree), and P, lds and the kernel the caller launches all
+// follow that one value.
+static int query_setup(rt_ctx* c, const char* what, RenderParams& P, size_t& lds, const rt_camera* view = nullptr,
+                       int call = -1, int* grid = nullptr) {
     HIPCHK(c, hipSetDevice(c->device));
     rt_camera cam{};
     cam.image_width = cam.image_height = 1;
-    fill_params(c, view ? view : &cam, 1, 1, plan_launch(c, true).mesh_stack, P);
+    const QueryPlan q = plan_job_query(c, call, view && grid && grid_in_reach(c, view));
+    fill_params(c, view ? view : &cam, 1, 1, q.mesh_stack, P);
     P.nodes = c->scene.d_nodes.as<Node>();   // (the time-binned copies are a render-kernel option)
-    lds = lds_scene_bytes_at(c, TRACE_BLOCK) + (size_t)TRACE_BLOCK * (size_t)P.mstack * 4;
+    apply_grid(c, q.grid, P);
+    lds = q.lds_bytes;
+    if (grid) *grid = q.grid;
     if (lds > 160 * 1024) return fail(c, RT_ERR_LIMIT, "%s needs %zu B of LDS per workgroup", what, lds);
     return RT_OK;
 }
@@ -1124,6 +1153,7 @@ int rt_camera_rays(rt_ctx* c, const rt_camera* cam, const rt_pixel_job* jobs, in
 struct JobQuery {
     RenderParams P;
     size_t lds;
+    int grid;   // what the call walks: 0 the tree, else TRAV_GRID [| TRAV_GFLAT] (plan_job_query)
     hipStream_t st;
     unsigned long long total;   // T = offsets[num_jobs] (c->d_px_offsets), where the list was scanned
 };
@@ -1132,14 +1162,14 @@ struct JobQuery {
 // camera; the call's own argument checks (`args`: RT_OK, or what fail returned); query_setup; then,
 // for a list that has jobs, the stream, ev0 and -- with `scan` -- pixel_scan.  A caller returns
 // what this returns where that is an error or num_jobs == 0.
-static int job_query_begin(rt_ctx* c, const char* what, const rt_camera* cam, const rt_pixel_job* jobs, int num_jobs,
-                           void* stream, bool scan, const std::function<int()>& args, JobQuery& q) {
+static int job_query_begin(rt_ctx* c, const char* what, int call, const rt_camera* cam, const rt_pixel_job* jobs,
+                           int num_jobs, void* stream, bool scan, const std::function<int()>& args, JobQuery& q) {
     if (!c) return RT_ERR_INVALID;
     if (!c->scene.has_scene) return fail(c, RT_ERR_NO_SCENE, "%s before rt_upload_scene", what);
     int rc = check_camera(c, cam);
     if (rc) return rc;
     if ((rc = args())) return rc;
-    if ((rc = query_setup(c, what, q.P, q.lds, cam))) return rc;
+    if ((rc = query_setup(c, what, q.P, q.lds, cam, call, &q.grid))) return rc;
     q.total = 0;
     if (num_jobs == 0) return RT_OK;
     q.st = stream_of(c, stream);
@@ -1176,7 +1206,8 @@ static int render_pixels(rt_ctx* c, const char* what, const rt_camera* cam, cons
                          uint32_t* out_segments, void* stream) {
     JobQuery q;
     // (max_depth <= 0 renders nothing and needs no scan)
-    int rc = job_query_begin(c, what, cam, jobs, num_jobs, stream, max_depth > 0, [&] {
+    int rc = job_query_begin(c, what, moments ? RT_QUERY_MOMENTS : RT_QUERY_PIXELS, cam, jobs, num_jobs, stream,
+                             max_depth > 0, [&] {
         if (num_jobs < 0 || (num_jobs > 0 && (!jobs || !out_sums || (moments && !out_sumsq))))
             return fail(c, RT_ERR_INVALID, "%s: %d jobs, jobs %p, out_sums %p, out_sumsq %p", what, num_jobs,
                         (const void*)jobs, out_sums, out_sumsq);
@@ -1222,7 +1253,7 @@ static int render_pixels(rt_ctx* c, const char* what, const rt_camera* cam, cons
                                                         (unsigned long long*)sum, flags, out_segments, sq, sqflags,
                                                         c->n_cu, c->tuning.grid_workgroups)
                             : launch_pixels_f32(P, lds, st, jobs, off, num_jobs, total, 0, (int)total,
-                                                (unsigned long long*)sum, flags, out_segments, c->n_cu);
+                                                (unsigned long long*)sum, flags, out_segments, c->n_cu, q.grid);
             if (e == hipSuccess) e = launch_pixels_finalize(off, num_jobs, acc, sum, flags, (float*)out_sums, st);
             if (e == hipSuccess && moments)
                 e = launch_pixels_finalize_moments(off, num_jobs, acc, sq, sqflags, (float*)out_sumsq, st);
@@ -1233,7 +1264,7 @@ static int render_pixels(rt_ctx* c, const char* what, const rt_camera* cam, cons
                 hipError_t pe = hipMemsetAsync(P.queue, 0, QUEUE_CTRL_BYTES, st);
                 if (pe == hipSuccess)
                     pe = launch_pixels_f64(P, lds, st, jobs, off, num_jobs, total, q0, (int)(q1 - q0), smp, sseg, c->n_cu,
-                                           moments ? c->tuning.grid_workgroups : 0);
+                                           q.grid, moments ? c->tuning.grid_workgroups : 0);
                 if (pe == hipSuccess)
                     pe = moments ? launch_pixels_reduce_moments(off, num_jobs, q0, q1, smp, sseg, acc, (double*)out_sums,
                                                                 (double*)out_sumsq, out_segments, st)
@@ -1265,7 +1296,7 @@ int rt_render_pixels_aov(rt_ctx* c, const rt_camera* cam, const rt_pixel_job* jo
                          const rt_aov_buffers* out, void* stream) {
     const char* what = "rt_render_pixels_aov";
     JobQuery q;
-    int rc = job_query_begin(c, what, cam, jobs, num_jobs, stream, true, [&] {
+    int rc = job_query_begin(c, what, RT_QUERY_AOV, cam, jobs, num_jobs, stream, true, [&] {
         if (num_jobs < 0 || (num_jobs > 0 && (!jobs || !out)))
             return fail(c, RT_ERR_INVALID, "%s: %d jobs, jobs %p, out %p", what, num_jobs, (const void*)jobs,
                         (const void*)out);

@@ -191,6 +191,17 @@ struct LaunchPlan {
     int wgs_per_cu;
 };
 LaunchPlan plan_launch(const rt_ctx* c, bool grid_in_reach);
+// rt_plan.cpp: what a job-list query (call: RT_QUERY_PIXELS rt_render_pixels, RT_QUERY_MOMENTS
+// rt_render_pixels_moments, RT_QUERY_AOV rt_render_pixels_aov; reported by rt_pixels_plan[_call])
+// runs for a camera whose reach proof gave grid_in_reach; call < 0: a per-ray query, the tree.  grid: 0 for the sphere tree, else TRAV_GRID or TRAV_GRID | TRAV_GFLAT -- the one
+// value the kernel's instantiation, lds_bytes and apply_grid's view of the scene all follow.
+// trav: that kernel's flags (0 for an fp64 tree); lds_bytes may exceed 160 KiB, which the
+// caller answers with RT_ERR_LIMIT (then the tree's does not fit either).
+struct QueryPlan {
+    int grid, trav, block, mesh_stack;
+    size_t lds_bytes;
+};
+QueryPlan plan_job_query(const rt_ctx* c, int call, bool grid_in_reach);
 int stack_entries(const rt_ctx* c);
 size_t lds_scene_bytes_at(const rt_ctx* c, int block, int tr = 0);
 

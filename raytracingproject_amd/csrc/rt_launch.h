@@ -36,6 +36,15 @@ hipError_t launch_render_f64(const RenderParams& P, size_t lds_bytes, hipStream_
 // -> n rt_hit; origin_ids: null, or per ray the input id of the primitive it starts on, looked
 // up in unmap (n_unmap entries)
 constexpr int TRACE_BLOCK = 256;
+// The traversal flags of the query kernels (TRAV_* by value: this header stands without
+// rt_device.h; rt_radiance.h checks them against the enum): fp32 spheres, fp32 meshes, fp64.  The
+// path kernel of rt_render_pixels (pixels_kernel; fp64: rt_render_pixels_moments' too) adds
+// QUERY_GRID, or QUERY_GRID | QUERY_GFLAT, where the call's plan walks the sphere grid (rt_ctx.h
+// plan_job_query) -- the `grid` argument of its launchers, 0 for the tree.  A mesh scene has no
+// grid instantiation: grid != 0 there is refused.  The fp32 moments kernel and the first-hit
+// kernels have none either: measured, the grid did not pay there.
+constexpr int QUERY_TRAV_SPHERES = 8 | 16 | 512, QUERY_TRAV_MESH = 8 | 512 | 8192, QUERY_TRAV_F64 = 32;
+constexpr int QUERY_GRID = 65536, QUERY_GFLAT = 131072;
 hipError_t launch_trace_f32(const RenderParams& P, size_t lds_bytes, hipStream_t stream, const void* rays, int n,
                             void* hits, const int* remap, const int* origin_ids, const int* unmap, int n_unmap,
                             bool diag);
@@ -83,11 +92,11 @@ hipError_t launch_camera_rays_f64(const RenderParams& P, hipStream_t stream, con
 hipError_t launch_pixels_f32(const RenderParams& P, size_t lds_bytes, hipStream_t stream, const void* jobs,
                              const unsigned long long* offsets, int num_jobs, unsigned long long total,
                              unsigned long long q_begin, int n,
-                             unsigned long long* acc, uint32_t* flags, uint32_t* segments, int n_cu);
+                             unsigned long long* acc, uint32_t* flags, uint32_t* segments, int n_cu, int grid);
 hipError_t launch_pixels_f64(const RenderParams& P, size_t lds_bytes, hipStream_t stream, const void* jobs,
                              const unsigned long long* offsets, int num_jobs, unsigned long long total,
                              unsigned long long q_begin, int n,
-                             double* samples, uint32_t* sample_segs, int n_cu, int max_wgs = 0);
+                             double* samples, uint32_t* sample_segs, int n_cu, int grid, int max_wgs = 0);
 // fp64: one pass's samples [q_begin, q_end) into out_sums / out_segments (may be null), per job
 // in sample order (pixels_reduce_kernel)
 hipError_t launch_pixels_reduce(const unsigned long long* offsets, int num_jobs, unsigned long long q_begin,
@@ -152,6 +161,13 @@ hipError_t launch_aov_reduce(const unsigned long long* offsets, int num_jobs, un
                              unsigned long long q_end, const double* records, const int32_t* record_ids,
                              int accumulate, void* carry, double* albedo, double* normal, double* depth, int32_t* id,
                              uint32_t* hits, hipStream_t stream);
+// rt_query_grid_f32.hip: launch_pixels_f32 for grid != 0 (it hands over): the fp32 sphere kernel
+// over the grid, kept out of the render kernels' translation unit.  P, lds_bytes and grid are one plan's (rt_ctx.h plan_job_query, rt_abi.cpp
+// apply_grid); a P that is not the grid's view of a sphere-only scene is hipErrorInvalidValue.
+hipError_t launch_pixels_grid_f32(const RenderParams& P, size_t lds_bytes, hipStream_t stream, const void* jobs,
+                                  const unsigned long long* offsets, int num_jobs, unsigned long long total,
+                                  unsigned long long q_begin, int n, unsigned long long* acc, uint32_t* flags,
+                                  uint32_t* segments, int n_cu, int grid);
 // rt_refine_jobs: jobs (rt_pixel_job, device) rewritten in place from sums / sumsq (num_jobs x 3
 // of elem_bytes 4 or 8) by rt_adaptive_params' fields; stats: two words, added to
 hipError_t launch_refine_jobs(void* jobs, int num_jobs, const void* sums, const void* sumsq, int elem_bytes,

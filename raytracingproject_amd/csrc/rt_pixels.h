@@ -8,8 +8,9 @@
 // kernel here reads or writes anything for it beyond its own output slots.
 //
 // pixels_kernel runs radiance_kernel's persistent loop (path_loop, rt_radiance.h: the per-XCD
-// heads, the tree walk with rt_trace_rays' flags, the bounce loop in both arithmetics); its own
-// are the start and the end of a path.  A claimed index is a flat sample q, not a
+// heads, the bounce loop in both arithmetics; the tree walk with rt_trace_rays' flags, or for a
+// sphere-only scene the sphere grid's walk added to them where the call's plan says so -- the
+// same hit either way); its own are the start and the end of a path.  A claimed index is a flat sample q, not a
 // ray (px_sample_start): the lane finds its job by a search in offsets, one per path (px_job_of:
 // interpolation, then bisection -- one or two round trips to an L2-resident array where the
 // counts are equal, at most ceil(log2(num_jobs + 1)) + 2 otherwise, against the 44 or 72 bytes

@@ -280,4 +280,39 @@ LaunchPlan plan_launch(const rt_ctx* c, bool grid_in_reach) {
     return r;
 }
 
+// A job-list query walks the sphere grid where a frame from the same camera would: a sphere-only
+// scene with a grid, the tuning's traversal asking for it (read now, as rt_render reads it),
+// the camera within the walk's reach, in fp64 an f64_kernel that resolves to a grid kernel (3 and
+// 4 force the tree, as for frames) -- and the grid's layout at TRACE_BLOCK within the LDS, else
+// the tree's, which may fit where the grid's does not.  Mesh and mixed scenes keep the tree: there
+// is no grid instantiation of the query kernels for them.
+// ...and where the grid was measured faster than the tree by more than the two spreads at every
+// sample count (C3, 1080p, depth 50, 2 and 16 spp; DESIGN.md §5 "Queries over the sphere grid"):
+// rt_render_pixels in both precisions and rt_render_pixels_moments in fp64 (pixels_kernel).  The
+// fp32 moments kernel (0.95 / 0.99 of the tree's time, within the spreads) and the first-hit call
+// (fp32 1.09 / 1.10; fp64 0.93 / 0.92, within the spreads at 2 spp) keep the tree, and have no
+// grid instantiation.
+static bool grid_pays(int call, bool f64) {
+    return call == RT_QUERY_PIXELS || (call == RT_QUERY_MOMENTS && f64);
+}
+
+QueryPlan plan_job_query(const rt_ctx* c, int call, bool grid_in_reach) {
+    const Planner p{c, c->scene.grid_nodes > 0 && grid_in_reach};
+    const bool f64 = c->precision == RT_PREC_F64, mesh = c->scene.n_mnodes > 0;
+    QueryPlan q;
+    q.block = TRACE_BLOCK;
+    q.mesh_stack = plan_launch(c, true).mesh_stack;
+    const size_t mstack = (size_t)TRACE_BLOCK * (size_t)q.mesh_stack * 4;
+    q.grid = 0;
+    if (!mesh && p.grid_usable && (c->tuning.traversal & TRAV_GRID) && grid_pays(call, f64)) {
+        const int k = p.f64_kernel_of();
+        if (!f64 || k == F64_KERNEL_GRID || k == F64_KERNEL_GRID_FLAT)
+            q.grid = TRAV_GRID | (p.grid_flat() ? TRAV_GFLAT : 0);
+    }
+    if (q.grid && lds_scene_bytes_at(c, TRACE_BLOCK, q.grid) + mstack > 160 * 1024) q.grid = 0;
+    q.lds_bytes = lds_scene_bytes_at(c, TRACE_BLOCK, q.grid) + mstack;
+    q.trav = f64 ? (q.grid ? QUERY_TRAV_F64 | q.grid : 0) : (mesh ? QUERY_TRAV_MESH : QUERY_TRAV_SPHERES) | q.grid;
+    return q;
+}
+
 }  // namespace rtx_abi

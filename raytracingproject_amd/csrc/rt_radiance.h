@@ -7,8 +7,12 @@
 //     scene (camera_cpu.h:19) -- the reference's ray_color bit for bit;
 //   * fp32: thr = thr * att, mul_rn(thr, sky), and every scattered segment names the primitive
 //     it starts on (self_id); the caller's first segment names none.
-// The tree is walked, never the sphere grid (whose reach proof is made per launch camera), with
-// the traversal flags of rt_trace_rays, so a ray's first segment finds what rt_trace_rays finds.
+// rt_radiance_rays walks the tree, never the sphere grid (whose reach proof is made per launch
+// camera, and these rays have none), with the traversal flags of rt_trace_rays, so a ray's first
+// segment finds what rt_trace_rays finds.  The job-list kernels that share path_loop
+// (rt_pixels.h, rt_moments.h) have a camera: for sphere-only scenes they are instantiated over
+// the grid as well (TRAV | TRAV_GRID, and | TRAV_GFLAT), and the call's plan (rt_plan.cpp
+// plan_job_query) picks one -- the same hit, so the same output bits.
 //
 // Paths last 1 .. max_depth segments, so lanes are persistent: a lane whose path has ended
 // takes the next unclaimed ray index and goes on in the same bounce loop.  The hand-out is per
@@ -33,6 +37,10 @@ struct PathKey {   // = rt_path_key (include/rt_hip.h)
     uint32_t pixel, sample, first_draw, pad;
 };
 static_assert(sizeof(PathKey) == 16, "rt_path_key");
+static_assert(QUERY_TRAV_SPHERES == (TRAV_SELROOT | TRAV_B128 | TRAV_CULL) &&
+                  QUERY_TRAV_MESH == (TRAV_SELROOT | TRAV_CULL | TRAV_MIFIF) && QUERY_TRAV_F64 == TRAV_F32BOX &&
+                  QUERY_GRID == TRAV_GRID && QUERY_GFLAT == TRAV_GFLAT,
+              "rt_launch.h names the query kernels' flags by value");
 
 // The persistent loop itself, shared by radiance_kernel, pixels_kernel (rt_pixels.h) and
 // pixels_moments_kernel (rt_moments.h): the scene load, the lane's path state, the claim from the
@@ -208,6 +216,45 @@ inline hipError_t launch_for_scene(const RenderParams& P, size_t lds_bytes, hipS
                                    int max_wgs, const Args&... args) {
     return P.n_mnodes > 0 ? launch_resident<MESH_KERNEL, BLOCK>(lds_bytes, stream, n, n_cu, max_wgs, P, args...)
                           : launch_resident<SPHERE_KERNEL, BLOCK>(lds_bytes, stream, n, n_cu, max_wgs, P, args...);
+}
+
+// static LDS bytes of a kernel (-1: the query failed)
+inline int kernel_static_lds(const void* kernel) {
+    hipFuncAttributes a;
+    return hipFuncGetAttributes(&a, kernel) == hipSuccess ? (int)a.sharedSizeBytes : -1;
+}
+// A sphere kernel over the grid.  The kernel's TRAV and the parameters the host sized for it must
+// be one pair: a grid kernel reads P.nodes as the grid, by LDS byte address from 0, and has no
+// traversal stack, so P must be what apply_grid (rt_abi.cpp) made of it -- the grid's header, no
+// stack, a sphere-only scene -- and the kernel must have no static LDS (asked once).  Anything
+// else is refused before the launch.
+template <auto KERNEL, int BLOCK, class... Args>
+inline hipError_t launch_grid_resident(const RenderParams& P, size_t lds_bytes, hipStream_t stream, int n, int n_cu,
+                                       int max_wgs, const Args&... args) {
+    static const int slds = kernel_static_lds((const void*)KERNEL);
+    if (slds != 0 || P.n_mnodes > 0 || P.stack_size != 0 || P.n_nodes <= 0 || P.grid.res[0] <= 0)
+        return hipErrorInvalidValue;
+    return launch_resident<KERNEL, BLOCK>(lds_bytes, stream, n, n_cu, max_wgs, P, args...);
+}
+// ... of the grid kernel a job-list query's plan names: grid = TRAV_GRID the 3-D walk, TRAV_GRID |
+// TRAV_GFLAT the flat walk (of a grid one cell tall in y).
+template <auto GRID_KERNEL, auto GFLAT_KERNEL, int BLOCK, class... Args>
+inline hipError_t launch_for_grid(const RenderParams& P, int grid, size_t lds_bytes, hipStream_t stream, int n,
+                                  int n_cu, int max_wgs, const Args&... args) {
+    if (grid == (TRAV_GRID | TRAV_GFLAT))
+        return P.grid.res[1] != 1
+                   ? hipErrorInvalidValue
+                   : launch_grid_resident<GFLAT_KERNEL, BLOCK>(P, lds_bytes, stream, n, n_cu, max_wgs, args...);
+    if (grid == TRAV_GRID) return launch_grid_resident<GRID_KERNEL, BLOCK>(P, lds_bytes, stream, n, n_cu, max_wgs, args...);
+    return hipErrorInvalidValue;
+}
+// ... and of its tree kernels (grid = 0, launch_for_scene), which take P as fill_params made it:
+// no grid header.
+template <auto MESH_KERNEL, auto SPHERE_KERNEL, int BLOCK, class... Args>
+inline hipError_t launch_for_tree(const RenderParams& P, size_t lds_bytes, hipStream_t stream, int n, int n_cu,
+                                  int max_wgs, const Args&... args) {
+    if (P.grid.res[0] != 0) return hipErrorInvalidValue;
+    return launch_for_scene<MESH_KERNEL, SPHERE_KERNEL, BLOCK>(P, lds_bytes, stream, n, n_cu, max_wgs, args...);
 }
 
 }  // namespace rtx

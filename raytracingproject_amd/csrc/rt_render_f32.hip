@@ -156,21 +156,26 @@ hipError_t launch_radiance_f32(const RenderParams& P, size_t lds_bytes, hipStrea
 }
 
 // Sparse rendering (rt_render_pixels), fp32: launch_radiance_f32's flags, register budgets and
-// grid; the camera and the job search are live only while a lane takes a sample.
+// grid; the camera and the job search are live only while a lane takes a sample.  grid: what the
+// call's plan walks (rt_launch.h); the kernels over the sphere grid are rt_query_grid_f32.hip's.
 hipError_t launch_pixels_f32(const RenderParams& P, size_t lds_bytes, hipStream_t stream, const void* jobs,
                              const unsigned long long* offsets, int num_jobs, unsigned long long total,
                              unsigned long long q_begin, int n,
-                             unsigned long long* acc, uint32_t* flags, uint32_t* segments, int n_cu) {
+                             unsigned long long* acc, uint32_t* flags, uint32_t* segments, int n_cu, int grid) {
     if (n <= 0) return hipSuccess;
     constexpr int B = TRACE_BLOCK;
-    constexpr int TS = TRAV_SELROOT | TRAV_B128 | TRAV_CULL, TM = TRAV_SELROOT | TRAV_CULL | TRAV_MIFIF;
-    return launch_for_scene<pixels_kernel<float, false, B, RADIANCE_MESH_WPE, TM, true>,
-                            pixels_kernel<float, false, B, RADIANCE_WPE, TS, false>, B>(
+    constexpr int TS = QUERY_TRAV_SPHERES, TM = QUERY_TRAV_MESH;
+    if (grid)
+        return launch_pixels_grid_f32(P, lds_bytes, stream, jobs, offsets, num_jobs, total, q_begin, n, acc, flags,
+                                      segments, n_cu, grid);
+    return launch_for_tree<pixels_kernel<float, false, B, RADIANCE_MESH_WPE, TM, true>,
+                           pixels_kernel<float, false, B, RADIANCE_WPE, TS, false>, B>(
         P, lds_bytes, stream, n, n_cu, 0, (const PixelJob*)jobs, offsets, num_jobs, total, q_begin, n, acc, flags,
         segments, (float*)nullptr, (uint32_t*)nullptr);
 }
 
-// rt_render_pixels_moments, fp32: launch_pixels_f32's flags, register budgets and grid.
+// rt_render_pixels_moments, fp32: launch_pixels_f32's tree flags, register budgets and grid (no
+// kernel over the sphere grid: its atomics hide what the walk saves).
 hipError_t launch_pixels_moments_f32(const RenderParams& P, size_t lds_bytes, hipStream_t stream, const void* jobs,
                                      const unsigned long long* offsets, int num_jobs, unsigned long long total,
                                      unsigned long long q_begin, int n, unsigned long long* acc, uint32_t* flags,
@@ -178,9 +183,9 @@ hipError_t launch_pixels_moments_f32(const RenderParams& P, size_t lds_bytes, hi
                                      int max_wgs) {
     if (n <= 0) return hipSuccess;
     constexpr int B = TRACE_BLOCK;
-    constexpr int TS = TRAV_SELROOT | TRAV_B128 | TRAV_CULL, TM = TRAV_SELROOT | TRAV_CULL | TRAV_MIFIF;
-    return launch_for_scene<pixels_moments_kernel<B, RADIANCE_MESH_WPE, TM, true>,
-                            pixels_moments_kernel<B, RADIANCE_WPE, TS, false>, B>(
+    constexpr int TS = QUERY_TRAV_SPHERES, TM = QUERY_TRAV_MESH;
+    return launch_for_tree<pixels_moments_kernel<B, RADIANCE_MESH_WPE, TM, true>,
+                           pixels_moments_kernel<B, RADIANCE_WPE, TS, false>, B>(
         P, lds_bytes, stream, n, n_cu, max_wgs, (const PixelJob*)jobs, offsets, num_jobs, total, q_begin, n, acc, flags,
         segments, sq, sqflags);
 }
@@ -192,9 +197,9 @@ static hipError_t launch_aov(const RenderParams& P, size_t lds_bytes, hipStream_
                              const unsigned long long* offsets, int num_jobs, unsigned long long total,
                              const int* remap, const AovAcc& A, int n_cu) {
     constexpr int B = TRACE_BLOCK;
-    constexpr int TS = TRAV_SELROOT | TRAV_B128 | TRAV_CULL, TM = TRAV_SELROOT | TRAV_CULL | TRAV_MIFIF;
-    return launch_for_scene<aov_kernel<float, false, B, RADIANCE_MESH_WPE, TM, true, COMBINE>,
-                            aov_kernel<float, false, B, RADIANCE_WPE, TS, false, COMBINE>, B>(
+    constexpr int TS = QUERY_TRAV_SPHERES, TM = QUERY_TRAV_MESH;
+    return launch_for_tree<aov_kernel<float, false, B, RADIANCE_MESH_WPE, TM, true, COMBINE>,
+                           aov_kernel<float, false, B, RADIANCE_WPE, TS, false, COMBINE>, B>(
         P, lds_bytes, stream, (int)total, n_cu, 0, jobs, offsets, num_jobs, total, 0ull, (int)total, remap, A,
         (float*)nullptr, (int32_t*)nullptr);
 }

@@ -317,17 +317,27 @@ hipError_t launch_camera_rays_f64(const RenderParams& P, hipStream_t stream, con
 }
 
 // Sparse rendering (rt_render_pixels), fp64: launch_radiance_f64's box tests, register budget
-// and grid.
+// and grid.  grid: what the call's plan walks (rt_launch.h) -- the cells chosen in fp32, the listed
+// spheres tested in fp64, as f64_kernel 5 / 6 walk them.
+constexpr int TQ3 = QUERY_TRAV_F64 | QUERY_GRID, TQF = TQ3 | QUERY_GFLAT;
 hipError_t launch_pixels_f64(const RenderParams& P, size_t lds_bytes, hipStream_t stream, const void* jobs,
                              const unsigned long long* offsets, int num_jobs, unsigned long long total,
                              unsigned long long q_begin, int n,
-                             double* samples, uint32_t* sample_segs, int n_cu, int max_wgs) {
+                             double* samples, uint32_t* sample_segs, int n_cu, int grid, int max_wgs) {
     if (n <= 0) return hipSuccess;
     constexpr int B = TRACE_BLOCK;
-    return launch_for_scene<pixels_kernel<double, true, B, 4, TRAV_F32BOX, true>,
-                            pixels_kernel<double, true, B, 4, TRAV_F32BOX, false>, B>(
-        P, lds_bytes, stream, n, n_cu, max_wgs, (const PixelJob*)jobs, offsets, num_jobs, total, q_begin, n,
-        (unsigned long long*)nullptr, (uint32_t*)nullptr, (uint32_t*)nullptr, samples, sample_segs);
+    const PixelJob* j = (const PixelJob*)jobs;
+    unsigned long long* const no_acc = nullptr;
+    uint32_t* const no_u32 = nullptr;
+    if (grid)
+        return launch_for_grid<pixels_kernel<double, true, B, 4, TQ3, false>,
+                               pixels_kernel<double, true, B, 4, TQF, false>, B>(
+            P, grid, lds_bytes, stream, n, n_cu, max_wgs, j, offsets, num_jobs, total, q_begin, n, no_acc, no_u32,
+            no_u32, samples, sample_segs);
+    return launch_for_tree<pixels_kernel<double, true, B, 4, QUERY_TRAV_F64, true>,
+                           pixels_kernel<double, true, B, 4, QUERY_TRAV_F64, false>, B>(
+        P, lds_bytes, stream, n, n_cu, max_wgs, j, offsets, num_jobs, total, q_begin, n, no_acc, no_u32, no_u32, samples,
+        sample_segs);
 }
 
 hipError_t launch_pixels_reduce(const unsigned long long* offsets, int num_jobs, unsigned long long q_begin,
@@ -399,10 +409,10 @@ hipError_t launch_aov_f64(const RenderParams& P, size_t lds_bytes, hipStream_t s
                           int n_cu) {
     if (n <= 0) return hipSuccess;
     constexpr int B = TRACE_BLOCK;
-    return launch_for_scene<aov_kernel<double, true, B, 4, TRAV_F32BOX, true, false>,
-                            aov_kernel<double, true, B, 4, TRAV_F32BOX, false, false>, B>(
-        P, lds_bytes, stream, n, n_cu, 0, (const PixelJob*)jobs, offsets, num_jobs, total, q_begin, n, remap, AovAcc{},
-        records, record_ids);
+    const PixelJob* j = (const PixelJob*)jobs;
+    return launch_for_tree<aov_kernel<double, true, B, 4, QUERY_TRAV_F64, true, false>,
+                           aov_kernel<double, true, B, 4, QUERY_TRAV_F64, false, false>, B>(
+        P, lds_bytes, stream, n, n_cu, 0, j, offsets, num_jobs, total, q_begin, n, remap, AovAcc{}, records, record_ids);
 }
 
 hipError_t launch_aov_reduce(const unsigned long long* offsets, int num_jobs, unsigned long long q_begin,

@@ -16,9 +16,17 @@ On the C3 scene (random spheres) at `--width` x 9/16 `--width`, max_depth `--dep
                  rt_render frame (the default kernel), whose own rt_last_kernel_ms is given for
                  comparison -- with, as the yardstick for that RMSE, the RMSE of a uniform rt_render
                  frame at the adaptive frame's mean spp (rounded up) against the same `--max`-spp frame.
+  (t) traversals the adaptive frame of (c), and the denoised frame's total (rt_render_pixels_moments
+                 + rt_render_pixels_aov + rt_denoise at `--denoise-spp`, the three calls'
+                 rt_last_kernel_ms added, as tools/denoise_probe.py adds them), each on a context with
+                 RT_TRAV_DEFAULT (the queries walk the sphere grid: rt_pixels_plan) and on one with
+                 RT_TRAV_DEFAULT & ~RT_TRAV_GRID (the tree), alternating, `--reps` times after a
+                 warm-up.  grid_wins: the tree's median exceeds the grid's by more than the two
+                 spreads.  (tools/pixels_probe.py --traversals has the single calls.)
 One JSON line per measurement.  There is no pass threshold.
 
 python tools/adaptive_probe.py [--parts a,b,c --width 1920 --spps 2,16 --reps 10 --out profiles/adaptive_probe.jsonl]
+python tools/adaptive_probe.py --parts t [--reps 10 --out profiles/adaptive_traversals.jsonl]
 """
 import argparse
 import json
@@ -141,6 +149,70 @@ def part_c(S, M, cam, a):
              "uniform_equal_rmse_vs_uniform_max": round(float(np.sqrt(np.mean((uni - ref) ** 2))), 6)}]
 
 
+def part_t(prec, S, M, cam, a):
+    import torch
+    f64 = prec == N.RT_PREC_F64
+    tdt = torch.float64 if f64 else torch.float32
+    W, H = cam.image_width, cam.image_height
+    npx = W * H
+    spp = a.denoise_spp
+    ctxs, plans = {}, {}
+    for name, trav in (("grid", N.RT_TRAV_DEFAULT), ("tree", N.RT_TRAV_DEFAULT & ~N.RT_TRAV_GRID)):
+        r = N.Renderer(0, 0x5EED, prec)
+        r.set_tuning(traversal=trav)
+        r.upload_scene(S, M)
+        p = r.pixels_plan(cam)
+        assert p.walks_grid == (1 if name == "grid" else 0), (name, p.walks_grid)
+        ctxs[name], plans[name] = r, {"traversal": p.traversal, "block": p.block, "lds_bytes": p.lds_bytes,
+                                  "walks_grid": {n: r.pixels_plan(cam, c).walks_grid for n, c in
+                                                 (("pixels", N.RT_QUERY_PIXELS), ("moments", N.RT_QUERY_MOMENTS),
+                                                  ("aov", N.RT_QUERY_AOV))}}
+    d_j = torch.from_numpy(jobs_of(np.arange(npx), spp).view(np.uint8)).to("cuda")
+    d_s, d_q, d_alb, d_nrm, d_out = (torch.empty((npx, 3), dtype=tdt, device="cuda") for _ in range(5))
+    d_z = torch.empty(npx, dtype=tdt, device="cuda")
+    d_hits = torch.empty(npx, dtype=torch.int32, device="cuda")
+    params = N.Renderer.denoise_params()
+    names = ("adaptive_wall", "denoised_total", "denoised_moments", "denoised_aov", "denoised_filter")
+    ms = {n: {k: [] for k in ctxs} for n in names}
+    shape = {}
+    for rep in range(a.reps + 1):   # (the first round warms up)
+        for k, r in ctxs.items():
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            d_as, _, d_n, rounds = r.render_adaptive(cam, a.depth, a.rel_error, a.abs_floor, a.min, a.max, a.max)
+            torch.cuda.synchronize()
+            t = {"adaptive_wall": (time.perf_counter() - t0) * 1e3}
+            shape[k] = (rounds, int(d_n.sum(dtype=torch.int64).item()))
+            r.render_pixels_moments(cam, d_j.data_ptr(), npx, a.depth, d_s.data_ptr(), d_q.data_ptr())
+            t["denoised_moments"] = r.last_kernel_ms()
+            r.render_pixels_aov(cam, d_j.data_ptr(), npx, d_alb.data_ptr(), d_nrm.data_ptr(), d_z.data_ptr(), None,
+                                d_hits.data_ptr())
+            t["denoised_aov"] = r.last_kernel_ms()
+            r.denoise(W, H, d_s.data_ptr(), d_out.data_ptr(), d_q.data_ptr(), None, spp, d_alb.data_ptr(),
+                      d_nrm.data_ptr(), d_z.data_ptr(), d_hits.data_ptr(), spp, params, None)
+            t["denoised_filter"] = r.last_kernel_ms()
+            t["denoised_total"] = t["denoised_moments"] + t["denoised_aov"] + t["denoised_filter"]
+            torch.cuda.synchronize()
+            if rep:
+                for n in names:
+                    ms[n][k].append(t[n])
+    for r in ctxs.values():
+        r.close()
+    assert shape["grid"] == shape["tree"], shape
+    line = {"part": "t", "scene": "c3", "precision": "fp64" if f64 else "fp32", "width": W, "height": H,
+            "max_depth": a.depth, "min_samples": a.min, "max_samples": a.max, "rel_error": a.rel_error,
+            "abs_floor": a.abs_floor, "denoise_spp": spp, "reps": a.reps, "rounds": shape["grid"][0],
+            "mean_spp": round(shape["grid"][1] / npx, 3), "plans": plans}
+    for n in names:
+        med = {k: float(np.median(v)) for k, v in ms[n].items()}
+        spread = {k: float(max(v) - min(v)) for k, v in ms[n].items()}
+        for k in med:
+            line[f"{n}_{k}_ms_median"], line[f"{n}_{k}_ms_spread"] = round(med[k], 4), round(spread[k], 4)
+        line[f"{n}_grid_over_tree"] = round(med["grid"] / med["tree"], 4)
+        line[f"{n}_grid_wins"] = bool(med["tree"] - med["grid"] > spread["grid"] + spread["tree"])
+    return [line]
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--parts", default="a,b,c")
@@ -154,6 +226,8 @@ def main():
     ap.add_argument("--rel-error", type=float, default=0.05)
     ap.add_argument("--abs-floor", type=float, default=0.01)
     ap.add_argument("--frames", type=int, default=3)
+    ap.add_argument("--denoise-spp", type=int, default=16, help="(t) samples per pixel of the denoised frame")
+    ap.add_argument("--t-precisions", default="fp32", help="(t) precisions")
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
     rtweekend.reset_stream()
@@ -180,6 +254,9 @@ def main():
         emit(part_b(S, M, cam, a.reps, a.depth))
     if "c" in parts:
         emit(part_c(S, M, cam, a))
+    if "t" in parts:
+        for pname in a.t_precisions.split(","):
+            emit(part_t(N.RT_PREC_F64 if pname == "fp64" else N.RT_PREC_F32, S, M, cam, a))
 
 
 if __name__ == "__main__":

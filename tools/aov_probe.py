@@ -13,10 +13,15 @@ one warm-up round:
             route.  Its buffers are 44 or 72 B of ray and key plus 72 B of rt_hit per sample:
             `--composed-spp` (default: the same spp) measures it at fewer samples where they do not
             fit, and the line says so (composed_spp, and the per-sample figures).
+  --traversals  instead of those: the fused call (the wave combine) on a context with
+            RT_TRAV_DEFAULT (the call walks the sphere grid: rt_pixels_plan) and on one with
+            RT_TRAV_DEFAULT & ~RT_TRAV_GRID (the tree), alternating.  grid_wins: the tree's median
+            exceeds the grid's by more than the two spreads.
 One JSON line per precision and spp with medians, spreads (max - min) and ratios.  There is no pass
 threshold: whether fused is below composed, and whether the combine pays, is the finding.
 
 python tools/aov_probe.py [--width 1920 --spp 2,16 --reps 5 --out profiles/aov_probe.jsonl]
+python tools/aov_probe.py --traversals [--spp 2,16 --reps 10 --out profiles/aov_traversals.jsonl]
 """
 import argparse
 import json
@@ -38,7 +43,7 @@ def jobs_of(pixel, count):
     return j
 
 
-def renderer(prec, S, M, combine):
+def renderer(prec, S, M, combine, traversal=None):
     old = os.environ.get("RT_AOV_COMBINE")
     os.environ["RT_AOV_COMBINE"] = "1" if combine else "0"   # (read at rt_create)
     try:
@@ -48,8 +53,57 @@ def renderer(prec, S, M, combine):
             del os.environ["RT_AOV_COMBINE"]
         else:
             os.environ["RT_AOV_COMBINE"] = old
+    if traversal is not None:
+        r.set_tuning(traversal=traversal)
     r.upload_scene(S, M)
     return r
+
+
+def measure_traversals(prec, S, M, cam, spp, reps):
+    import torch
+    f64 = prec == N.RT_PREC_F64
+    tdt = torch.float64 if f64 else torch.float32
+    npx = cam.image_width * cam.image_height
+    d_jobs = torch.from_numpy(jobs_of(np.arange(npx), spp).view(np.uint8)).to("cuda")
+    ctxs = {"grid": renderer(prec, S, M, True, N.RT_TRAV_DEFAULT),
+            "tree": renderer(prec, S, M, True, N.RT_TRAV_DEFAULT & ~N.RT_TRAV_GRID)}
+    plans = {}
+    for k, r in ctxs.items():
+        p = r.pixels_plan(cam)
+        assert p.walks_grid == (1 if k == "grid" else 0), (k, p.walks_grid)
+        plans[k] = {"traversal": p.traversal, "block": p.block, "lds_bytes": p.lds_bytes,
+                                  "walks_grid": {n: r.pixels_plan(cam, c).walks_grid for n, c in
+                                                 (("pixels", N.RT_QUERY_PIXELS), ("moments", N.RT_QUERY_MOMENTS),
+                                                  ("aov", N.RT_QUERY_AOV))}}
+    d_alb = torch.empty((npx, 3), dtype=tdt, device="cuda")
+    d_nrm = torch.empty((npx, 3), dtype=tdt, device="cuda")
+    d_dep = torch.empty(npx, dtype=tdt, device="cuda")
+    d_id = torch.empty(npx, dtype=torch.int32, device="cuda")
+    d_hits = torch.empty(npx, dtype=torch.int32, device="cuda")
+    torch.cuda.synchronize()
+    ms, hits = {k: [] for k in ctxs}, {}
+    for rep in range(reps + 1):   # (the first round warms up)
+        for k, r in ctxs.items():
+            r.render_pixels_aov(cam, d_jobs.data_ptr(), npx, d_alb.data_ptr(), d_nrm.data_ptr(), d_dep.data_ptr(),
+                                d_id.data_ptr(), d_hits.data_ptr())
+            t = r.last_kernel_ms()
+            hits[k] = int(d_hits.sum(dtype=torch.int64).item())
+            if rep:
+                ms[k].append(t)
+    for r in ctxs.values():
+        r.close()
+    assert hits["grid"] == hits["tree"], hits
+    med = {k: float(np.median(v)) for k, v in ms.items()}
+    spread = {k: float(max(v) - min(v)) for k, v in ms.items()}
+    line = {"probe": "aov-traversals", "scene": "c3", "precision": "fp64" if f64 else "fp32", "width": cam.image_width,
+            "height": cam.image_height, "spp": spp, "samples": npx * spp, "reps": reps, "hits": hits["grid"],
+            "plans": plans}
+    for k in ms:
+        line[f"aov_{k}_ms_median"] = round(med[k], 4)
+        line[f"aov_{k}_ms_spread"] = round(spread[k], 4)
+    line["aov_grid_over_tree"] = round(med["grid"] / med["tree"], 4)
+    line["aov_grid_wins"] = bool(med["tree"] - med["grid"] > spread["grid"] + spread["tree"])
+    return line
 
 
 def measure(prec, S, M, cam, spp, cspp, reps):
@@ -119,6 +173,7 @@ def main():
     ap.add_argument("--composed-spp", type=int, default=0, help="cap on the composed route's spp (0: none)")
     ap.add_argument("--reps", type=int, default=5)
     ap.add_argument("--precisions", default="fp32,fp64")
+    ap.add_argument("--traversals", action="store_true", help="the grid against the tree instead of the routes")
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
     rtweekend.reset_stream()
@@ -130,7 +185,9 @@ def main():
     for pname in a.precisions.split(","):
         for spp in (int(s) for s in a.spp.split(",")):
             cspp = min(spp, a.composed_spp) if a.composed_spp > 0 else spp
-            line = measure(N.RT_PREC_F64 if pname == "fp64" else N.RT_PREC_F32, S, M, cam, spp, cspp, a.reps)
+            prec = N.RT_PREC_F64 if pname == "fp64" else N.RT_PREC_F32
+            line = (measure_traversals(prec, S, M, cam, spp, a.reps) if a.traversals
+                    else measure(prec, S, M, cam, spp, cspp, a.reps))
             print(json.dumps(line), flush=True)
             lines.append(line)
     if a.out:
