@@ -227,6 +227,28 @@ def build_batch_cull(verbose: bool = False) -> list[Path]:
     return exes
 
 
+DEPTH_EXE = OBJ / "san" / "cand_depth_driver"
+DEPTH_MUTANTS = (1, 2, 3, 4)   # RT_CULL_MUTATE: CULL_MUTANTS' three, and the packed bound rounded up
+
+
+def build_cand_depth(verbose: bool = False) -> list[Path]:
+    """tests/cpp/cand_depth_driver.cpp (the candidates' near bound of csrc/rt_batch_cull.h --
+    cull_near, the packed list word and its order -- against the fp32 roots of brute-forced camera
+    rays; run by tests/test_cand_depth.py) under the same sanitizers as build_sanitize: the driver
+    itself, then one copy per mutation of the bound, each of which the driver must catch.  No GPU
+    code."""
+    src = ROOT / "tests" / "cpp" / "cand_depth_driver.cpp"
+    deps = [CSRC / "rt_batch_cull.h", CSRC / "rt_scene.h"]
+    exes = [DEPTH_EXE] + [DEPTH_EXE.with_name(f"cand_depth_driver_m{m}") for m in DEPTH_MUTANTS]
+
+    def one(k: int) -> None:
+        _build_san(exes[k], [src], deps, ["-O2", "-ffp-contract=off", f"-DRT_CULL_MUTATE={k}", f"-I{CSRC}"], verbose)
+
+    with ThreadPoolExecutor(max_workers=4) as ex:
+        list(ex.map(one, range(len(exes))))
+    return exes
+
+
 def build_oracle(verbose: bool = False) -> None:
     """Compile the C restatement (test infrastructure) and, where /root/reference is
     present, the reference driver into oracle/_ref (test infrastructure: oracle/_ref/

@@ -39,10 +39,39 @@
 //    sum each carry a factor CULL_UP = 1 + 2^-19; k > 7/8 (or L = 0, or a NaN anywhere in the
 //    camera words) keeps every sphere.
 // Both comparisons are written so that a NaN keeps the sphere.
+//
+// The near bound (r21, cull_near).  A ray's parameter lam is the kernel's t: it traces
+// o + t (sample - o).  The first condition above also bounds a hit from below:
+//   lam L >= s - rb - D(lam) >= s - W - lam L k,   so   lam >= (s - W) / (L (1 + k)):
+// no camera ray of the tile reaches the sphere before that parameter, at any time in [0, 1).
+// A candidate list ordered by this bound can stop at the first candidate whose bound lies
+// beyond every lane's closest hit (rt_device.h closest_hit CAND).
+// Rounding: the bound has to hold for the root the kernel's sphere_root reports, not for the
+// exact one, so the point the kernel takes for the hit may lie off the sphere by eps, and the
+// condition reads |s - lam L| <= rb + D(lam) + eps.  eps has two parts:
+//  * what the margin mg above already covers: the displaced ray (E), s and q (16 u |q|), and
+//    the root's own relative error -- the pair c / q, q / a and the approximate rcp are good
+//    to a few u of the root, a distance of a few u (|q| + rb) along the ray; c = |f|^2 - r^2
+//    cancels where the origin lies near the surface, to 4 u |f|^2 / (2 |f|), the same order;
+//  * the discriminant.  disc = r^2 - |l|^2 carries |d disc| < 32 u r (|o| + |C|) + 4 u r^2
+//    (dl above), and the half chord sqrt(disc) it yields is off by at most sqrt(|d disc|)
+//    -- all of it near grazing, where disc is small and the error passes through the square
+//    root.  The far root moves by that distance, and the near root c / q by the same relative
+//    amount, less in distance.  sqrt(|d disc|) < sqrt(64 u rb (|q| + scale + rb))
+//    = 2^-9 sqrt(rb (...)); G = CULL_SQ sqrt(rb (|q| + scale + rb)) with CULL_SQ = 2^-8 is
+//    taken off as well.  (A ray that misses the exact sphere and is reported as a hit has
+//    disc within d disc of zero: the same bound on the point it reports.)
+//  * nd = 1 / (L (1 + k)) is rounded down by CULL_UP^2 (iL, the sum, the quotient: a few u
+//    each), the product by CULL_DN = 1 - 2^-19; the result is clamped to >= 0, and is 0 for a
+//    NaN anywhere and for a beam that drops nothing (!ok).
+//  * packing (cand_pack) clears the low 12 bits of the fp32 pattern: for a value >= 0 that
+//    is truncation toward zero, downward.
+// So cull_near, before and after packing, is at most every root sphere_root reports.
 #pragma once
 #include <cmath>
 #include <cstddef>
 #include <cstdint>
+#include <cstring>
 
 #include "rt_scene.h"
 
@@ -56,21 +85,29 @@ static_assert((BATCH_CAND_CAP + 1) * 4 <= BATCH_CAND_BYTES, "candidate list");
 
 // tests/cpp/batch_cull_driver.cpp only: 1 shrinks the rounding margins to nothing, 2 drops
 // the lens radius, 3 drops the motion's half-length -- each must make the driver fail
+// (tests/cpp/cand_depth_driver.cpp: the same three, and 4: the packed bound rounded up)
 #ifndef RT_CULL_MUTATE
 #define RT_CULL_MUTATE 0
 #endif
 #if RT_CULL_MUTATE == 1
 constexpr float CULL_EPS = 0x1p-29f, CULL_EPS_CAM = 0x1p-31f, CULL_UP = 1.f;
+constexpr float CULL_SQ = 0x1p-20f, CULL_DN = 1.f;
 #else
 constexpr float CULL_EPS = 0x1p-17f, CULL_EPS_CAM = 0x1p-19f, CULL_UP = 1.f + 0x1p-19f;
+constexpr float CULL_SQ = 0x1p-8f, CULL_DN = 1.f - 0x1p-19f;
 #endif
+// a packed list word (r21): the near bound's upper 20 bits over the record's index in the LDS
+// sphere array (< 4096: rt_scene.h's limits, asserted where the list is built)
+constexpr uint32_t CAND_IDX_BITS = 12, CAND_IDX_MASK = (1u << CAND_IDX_BITS) - 1u;
 
 // what the tile's rays share: the axis (from c along the unit vector ax), the widened lens
-// radius, k / (1 - k), the scale of the camera words; ok: a sphere may be dropped at all
+// radius, k / (1 - k), the scale of the camera words; ok: a sphere may be dropped at all;
+// nd: 1 / (L (1 + k)) rounded down (cull_near)
 struct CullBeam {
     float c[3], ax[3];
     float rl, g, scale;
     bool ok;
+    float nd;
 };
 
 // cam: CohConst::cam (f_center, f_p00, f_du, f_dv, f_ddu, f_ddv); (tx0, ty0): the tile's
@@ -101,6 +138,7 @@ RT_HD inline CullBeam cull_beam(const float* cam, int defocus, int tx0, int ty0)
     const float k = (b.rl + rho) * iL * CULL_UP;
     b.ok = k <= 0.875f;   // (false for NaN and for L = 0)
     b.g = k / (1.f - k) * CULL_UP * CULL_UP;
+    b.nd = iL / ((1.f + k) * CULL_UP * CULL_UP);
     return b;
 }
 
@@ -121,6 +159,48 @@ RT_HD inline bool cull_keep(const CullBeam& b, const SphereF& s) {
     const float bound = (W + b.g * fmaxf(sa + W, 0.f)) * CULL_UP;
     const bool behind = sa < -W, outside = perp > bound;   // (false for NaN)
     return !b.ok || !(behind || outside);
+}
+
+// at most every root the kernel's fp32 sphere test reports for a camera ray of the beam's tile
+// against the sphere, at any time in [0, 1); >= 0, and 0 where nothing is known (the text above)
+RT_HD inline float cull_near(const CullBeam& b, const SphereF& s) {
+    const float hx = 0.5f * s.cv[0], hy = 0.5f * s.cv[1], hz = 0.5f * s.cv[2];
+#if RT_CULL_MUTATE == 3
+    const float rb = fabsf(s.r);
+#else
+    const float rb = fabsf(s.r) + sqrtf(hx * hx + hy * hy + hz * hz) * CULL_UP;
+#endif
+    const float qx = (s.c[0] + hx) - b.c[0], qy = (s.c[1] + hy) - b.c[1], qz = (s.c[2] + hz) - b.c[2];
+    const float qn = sqrtf(qx * qx + qy * qy + qz * qz);
+    const float sa = qx * b.ax[0] + qy * b.ax[1] + qz * b.ax[2];
+    const float W = (rb + b.rl) + CULL_EPS * (qn + b.scale + rb);
+    const float G = CULL_SQ * sqrtf(rb * (qn + b.scale + rb));
+    const float near = ((sa - W) - G) * b.nd * CULL_DN;
+    return b.ok && near > 0.f ? near : 0.f;   // (0 for NaN)
+}
+
+// the list word of record k with near bound `near` (>= 0), and its two halves
+RT_HD inline uint32_t cand_pack(float near, uint32_t k) {
+    uint32_t u;
+    memcpy(&u, &near, 4);
+#if RT_CULL_MUTATE == 4
+    u += CAND_IDX_MASK;
+#endif
+    return (u & ~CAND_IDX_MASK) | k;
+}
+RT_HD inline float cand_near(uint32_t w) {
+    w &= ~CAND_IDX_MASK;
+    float f;
+    memcpy(&f, &w, 4);
+    return f;
+}
+RT_HD inline uint32_t cand_index(uint32_t w) { return w & CAND_IDX_MASK; }
+// a word's place in the ascending order of the n list words: how many are smaller.  The words
+// differ in their index bits, so the places are a permutation, ordered by (near, index).
+RT_HD inline uint32_t cand_rank(const uint32_t* words, uint32_t n, uint32_t w) {
+    uint32_t r = 0;
+    for (uint32_t j = 0; j < n; ++j) r += words[j] < w;
+    return r;
 }
 
 // the predicate as one call: cam words, tile, sphere record

@@ -306,6 +306,13 @@ static_assert(sizeof(CohEntryD<false>) == 16 && sizeof(CohEntryD<true>) == 24, "
 #ifndef RT_POP_THROUGH
 #define RT_POP_THROUGH 1
 #endif
+// Compile-time switch of r21, the same way (DESIGN.md section 5 "Round 21"; at 0 the kernels are
+// r20's, instruction for instruction): RT_CAND_DEPTH (the coh_cands kernels' candidate lists are
+// ordered by a near bound of each sphere's roots, rt_batch_cull.h cull_near, and closest_hit's
+// candidate loop stops at the first candidate no lane's closest hit reaches)
+#ifndef RT_CAND_DEPTH
+#define RT_CAND_DEPTH 1
+#endif
 // r13, the fp32 sphere-grid kernels (coh_rng0): the entry also carries the path's RNG state
 // right after CounterRng::start, as the batch computed it, so that the pop sets it instead of
 // hashing pixel and sample again.  One 16-byte LDS write and one 16-byte LDS read per entry.
@@ -728,6 +735,7 @@ __device__ __forceinline__ void keep_live(uint32_t v) { asm volatile("" ::"v"(v)
 // nothing else -- no front list, no grid.  The caller's list holds every sphere of the LDS
 // array the ray can hit (rt_batch_cull.h), the test is test_rec with the walk's arguments,
 // and the closest hit does not depend on the order of the tests: the walk's hit, bit for bit.
+// (RT_CAND_DEPTH, r21: the list holds packed words in ascending order of a near bound, below.)
 template <class R, bool EXACT, bool DIAG = false, int TRAV = 0, bool MESH = false, bool SUSP = false,
           bool CAND = false>
 __device__ __forceinline__ Hit<R> closest_hit(const SceneView<R>& sc, const Ray<R>& ray, uint16_t* stack, int stride,
@@ -830,7 +838,40 @@ __device__ __forceinline__ Hit<R> closest_hit(const SceneView<R>& sc, const Ray<
                                      ray.time, TMIN, tlim, !EXACT && is_self, tk);
     };
     auto test_one = [&](int k, R tlim, R& tk) -> bool { return test_rec(sc.sph + k, k == self_id, tlim, tk); };
-    if constexpr (CAND) {
+    if constexpr (CAND && RT_CAND_DEPTH) {
+        // r21: the list's words (rt_batch_cull.h cand_pack) stand in ascending order of their
+        // near bounds -- no root of any of the wave's rays on that sphere lies below it -- so
+        // the loop ends at the first candidate whose bound no lane's closest hit reaches: every
+        // later one's is no smaller.  (>=, not >: a root equal to the closest hit still wins
+        // over a higher record.)  The closest hit no longer meets the records in ascending order,
+        // so among equal roots the lower record is kept by the test's limit: a record below the
+        // one that set tmax is tested against the next fp32 value above tmax (tmax is a positive
+        // finite root there, so that is its bit pattern + 1), which admits a root == tmax and
+        // nothing else new -- what the ascending loop's strict < did.  The big spheres, tested
+        // before the list, keep an equal root against every record: hit_k stays 0, which
+        // precedes nothing.  The word is unpacked on the scalar side; the exit test is one
+        // compare of tmax.
+        static_assert((TRAV & TRAV_B128) != 0 && (TRAV & TRAV_SELROOT) != 0, "the coh_cands kernels' sphere test");
+        const uint32_t sph0 = (uint32_t)sc.n_nodes * (uint32_t)sizeof(Node);
+        uint32_t hit_k = 0;   // the hit record's index + 1
+        for (int i = 0; i < ncand; ++i) {
+            const uint32_t w = (uint32_t)__builtin_amdgcn_readfirstlane(
+                (int)*(const lds_cu32*)(uintptr_t)(clist + 4u * (uint32_t)i));
+            if (!__builtin_amdgcn_ballot_w64(tmax >= __uint_as_float(w & ~CAND_IDX_MASK))) break;
+            if (DIAG) DiagCounters::count(dg->leaf_it, dg->leaf_act), ++dg->steps;
+            const uint32_t k1 = (w & CAND_IDX_MASK) + 1u;
+            const Sph* rec = (const Sph*)(const float4*)(const lds_cf4*)(uintptr_t)(sph0 + (k1 - 1u) * (uint32_t)sizeof(Sph));
+            const R tlim = __uint_as_float(__float_as_uint(tmax) + (k1 < hit_k ? 1u : 0u));
+            R t;
+            if (test_rec(rec, false, tlim, t)) {
+                tmax = t;
+                hit_k = k1;
+            }
+        }
+        if (hit_k) h.id = (int)hit_k - 1;
+        h.t = tmax;
+        return h;
+    } else if constexpr (CAND) {
         // one record per iteration, the same for every lane: the list entry and the record
         // are read from wave-uniform LDS addresses, the loop count is scalar
         uint32_t hit_off = 0xffffffffu;

@@ -663,6 +663,27 @@ __device__ __forceinline__ void render_coherent(const RenderParams& P0, const Sc
                         n += (uint32_t)__popcll(km);
                     }
                     if (n > (uint32_t)cap) n = 0xffffffffu;
+                    if constexpr (RT_CAND_DEPTH) {
+                        // r21: the list as packed words (rt_batch_cull.h cand_pack: the record's index
+                        // under its near bound) in ascending order, that is by (near, index).  Lane i
+                        // takes entry i, computes its record's bound, counts the smaller words
+                        // (cand_rank, the words read from the lanes that hold them) and stores its own
+                        // at that place.  Once per item of item_samples batches.
+                        static_assert(MAX_LEAF_FIRST + MAX_BIG <= (int)CAND_IDX_MASK, "list word: 12 index bits");
+                        if (n <= (uint32_t)BATCH_CAND_CAP) {
+                            __builtin_amdgcn_wave_barrier();
+                            const bool has = (uint32_t)lane < n;
+                            uint32_t w = 0xffffffffu;
+                            if (has) {
+                                const uint32_t k = (clist[lane] - sph0) / (uint32_t)sizeof(SphereF);
+                                w = cand_pack(cull_near(bm, sc.sph[k]), k);
+                            }
+                            uint32_t r = 0;
+                            for (uint32_t j = 0; j < n; ++j) r += (uint32_t)__builtin_amdgcn_readlane((int)w, (int)j) < w;
+                            __builtin_amdgcn_wave_barrier();
+                            if (has) clist[r] = w;
+                        }
+                    }
                 }
                 if (lane == 0) clist[BATCH_CAND_CAP] = n;
                 __builtin_amdgcn_wave_barrier();
