@@ -40,7 +40,7 @@ UNITS = {
     "rt_comm.cpp": [],
 }
 HEADERS = ["rt_device.h", "rt_render_impl.h", "rt_occluded.h", "rt_radiance.h", "rt_pixels.h", "rt_moments.h", "rt_aov.h", "rt_scene.h", "rt_launch.h", "rt_bvh.h", "rt_lbvh.h", "rt_ctx.h", "rt_devbuf.h",
-           "rt_treelet.h", "rt_pack.h", "rt_batch_cull.h", "rt_denoise.h", "rt_quant.h"]
+           "rt_treelet.h", "rt_pack.h", "rt_batch_cull.h", "rt_denoise.h", "rt_quant.h", "rt_trav.h"]
 
 
 def _stale(target: Path, deps: list[Path]) -> bool:

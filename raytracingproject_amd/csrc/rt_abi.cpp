@@ -275,7 +275,7 @@ int rt_set_tuning(rt_ctx* c, const rt_tuning* t) {
                                        "per CU), 0 (the compiler's register budget) or 6 (<= 80 VGPRs); 5 / 7 / 8 "
                                        "are not built (7 spilled inside the traversal loop: C4 +19 %)");
     if (t->coh_refill < 1 || t->coh_refill > 64) return fail(c, RT_ERR_INVALID, "coh_refill %d (1..64)", t->coh_refill);
-    if (t->f64_kernel != 0 && (t->f64_kernel == F64_KERNEL_GRID_FLAT || render_f64_block(t->f64_kernel) < 0))
+    if (t->f64_kernel != 0 && (t->f64_kernel == F64_KERNEL_GRID_FLAT || !find_render_f64(t->f64_kernel, false)))
         return fail(c, RT_ERR_INVALID, "f64_kernel %d (0 = default, or an instantiated one)", t->f64_kernel);
     if (t->front_spheres < -1 || t->front_spheres > 16)
         return fail(c, RT_ERR_INVALID, "front_spheres %d (-1 = auto, 0..16)", t->front_spheres);
@@ -314,8 +314,8 @@ int rt_set_tuning(rt_ctx* c, const rt_tuning* t) {
     if (t->mesh_builder != RT_MESH_BUILD_HOST && t->mesh_builder != RT_MESH_BUILD_GPU &&
         t->mesh_builder != RT_MESH_BUILD_GPU_LBVH)
         return fail(c, RT_ERR_INVALID, "mesh_builder %d", t->mesh_builder);
-    if (!render_f32_supported(t->block, t->waves_per_eu, t->traversal & ~(TRAV_MIFIF | TRAV_MWHILE | TRAV_GFLAT | TRAV_G3D),
-                              false))
+    if (!find_render_f32(t->block, t->waves_per_eu, t->traversal & ~(TRAV_MIFIF | TRAV_MWHILE | TRAV_GFLAT | TRAV_G3D),
+                         false, false))
         return fail(c, RT_ERR_INVALID, "no fp32 kernel instantiated for block %d, waves_per_eu %d, traversal %d",
                     t->block, t->waves_per_eu, t->traversal);
     const rt_tuning old = c->tuning;
@@ -653,8 +653,8 @@ static double item_balance_of(const rt_ctx* c, double lanes, double pixels) {
 // One fp32 launch of P.spp <= FIX_LAUNCH_SAMPLES samples from P.sample_begin: lanes add their
 // chunk's fixed-point sums into the context's accumulator for this buffer (integer atomics:
 // order-free), finalize_kernel writes out_sums.  e: the first launch error.
-static int render_range_f32(rt_ctx* c, const LaunchPlan& plan, RenderParams P, size_t npx, hipStream_t st,
-                            hipError_t& e) {
+static int render_range_f32(rt_ctx* c, const LaunchPlan& plan, const RenderKernel& k, RenderParams P, size_t npx,
+                            hipStream_t st, hipError_t& e) {
     float* out_sums = (float*)P.out_sums;
     int rc;
     rt_ctx::Accum* slot = nullptr;
@@ -706,9 +706,7 @@ static int render_range_f32(rt_ctx* c, const LaunchPlan& plan, RenderParams P, s
         // finalized to, restarted from the floats elsewhere (a reallocated buffer)
         e = launch_reconcile_accum(out_sums, acc, flags, npx, st);
     }
-    if (e == hipSuccess && P.spp > 0)
-        e = c->diag_buf ? launch_render_f32_diag(P, plan.lds_bytes, st, plan.trav, plan.block, plan.wpe)
-                        : launch_render_f32(P, plan.lds_bytes, st, plan.block, plan.wpe, plan.trav);
+    if (e == hipSuccess && P.spp > 0) e = launch_render(k, P, plan.lds_bytes, st);
     if (e == hipSuccess) e = launch_finalize(acc, accp, flags, out_sums, npx, st);
     return RT_OK;
 }
@@ -716,8 +714,8 @@ static int render_range_f32(rt_ctx* c, const LaunchPlan& plan, RenderParams P, s
 // fp64 on persistent lanes (TRAV_PERSIST): every sample's radiance goes to d_samples, then
 // the ordered reduction; passes bound the buffer to sample_buffer_mb (a shard with no tiles
 // has nothing to store: npx = 0)
-static int render_range_f64(rt_ctx* c, const LaunchPlan& plan, const RenderParams& P, size_t npx, hipStream_t st,
-                            hipError_t& e) {
+static int render_range_f64(rt_ctx* c, const LaunchPlan& plan, const RenderKernel& k, const RenderParams& P,
+                            size_t npx, hipStream_t st, hipError_t& e) {
     const int spp = P.spp;
     const size_t eb = elem_bytes(c);
     int rc;
@@ -741,7 +739,7 @@ static int render_range_f64(rt_ctx* c, const LaunchPlan& plan, const RenderParam
         const double lanes = (double)Q.max_wgs * plan.block;
         plan_phases(Q, Q.spp, lanes, (double)npx, balance, item_cap(c, plan.trav, lanes, (double)npx));
         e = hipMemsetAsync(Q.queue, 0, QUEUE_CTRL_BYTES, st);
-        if (e == hipSuccess) e = launch_render_f64(Q, plan.lds_bytes, st, plan.f64_kernel);
+        if (e == hipSuccess) e = launch_render(k, Q, plan.lds_bytes, st);
         if (e == hipSuccess)
             e = launch_reduce(c->d_samples.p, P.out_sums, (int)eb, npx * 3, Q.spp, (P.accumulate || done > 0) ? 1 : 0, st);
     }
@@ -766,24 +764,26 @@ int rt_render_range(rt_ctx* c, const rt_camera* cam, int sample_begin, int spp, 
     const LaunchPlan plan = plan_launch(c, grid_in_reach(c, cam));
     if (plan.lds_bytes > 160 * 1024)
         return fail(c, RT_ERR_LIMIT, "render needs %zu B of LDS per workgroup", plan.lds_bytes);
-    if (f32 && mesh && !render_f32_supported(plan.block, plan.wpe, plan.trav, true))
+    // the kernel that runs: the plan's, or with rt_render_diag's buffer set its instrumented copy
+    const RenderKernel* k =
+        f32 && c->diag_buf ? find_render_f32(plan.block, plan.wpe, plan.trav, mesh, true) : plan.kernel;
+    if (f32 && mesh && !plan.kernel)
         return fail(c, RT_ERR_INVALID, "no mesh kernel instantiated for block %d, mesh_waves_per_eu %d, traversal %d",
                     plan.block, plan.wpe, plan.trav);
-    if (f32 && !mesh && !render_f32_supported(plan.block, c->tuning.waves_per_eu, plan.trav, false))
+    if (f32 && !mesh && !plan.kernel)
         return fail(c, RT_ERR_INVALID,
                     "no fp32 kernel instantiated for block %d, waves_per_eu %d, traversal %d (tuning traversal %d; "
                     "128 = no LDS sums is added where they would cost occupancy)",
                     plan.block, c->tuning.waves_per_eu, plan.trav, c->tuning.traversal);
-    if (f32 && c->diag_buf && !render_f32_diag_supported(plan.block, plan.wpe, plan.trav, mesh))
+    if (f32 && c->diag_buf && !k)
         return fail(c, RT_ERR_INVALID, "no instrumented build of block %d, waves_per_eu %d, traversal %d (rt_render_diag)",
                     plan.block, plan.wpe, plan.trav);
+    if (!k) return fail(c, RT_ERR_INVALID, "no fp64 kernel instantiated for f64_kernel %d", plan.f64_kernel);
     if (plan.trav & TRAV_GRID) {
         // the grid walk reads cells and records by LDS byte address, counting from 0: the
         // kernel's dynamic LDS must start there, i.e. the kernel has no static LDS (rt_device.h)
-        // (the instrumented copy is another kernel: rt_render_diag launches it instead)
-        const int s = !f32 ? render_f64_static_lds(mesh, plan.f64_kernel)
-                      : c->diag_buf ? render_f32_diag_static_lds(plan.block, plan.wpe, plan.trav, mesh)
-                                    : render_f32_static_lds(plan.block, plan.wpe, plan.trav, mesh);
+        // (the instrumented copy is another kernel, with its own)
+        const int s = render_kernel_attrs(k).static_lds;
         if (s != 0) return fail(c, RT_ERR_HIP, "grid render kernel with %d B of static LDS (needs none)", s);
     }
     RenderParams P;
@@ -810,7 +810,8 @@ int rt_render_range(rt_ctx* c, const rt_camera* cam, int sample_begin, int spp, 
         P.sample_begin = sample_begin + done;
         P.spp = std::min(spp - done, range);
         P.accumulate = accumulate || done > 0 ? 1 : 0;
-        if ((rc = f32 ? render_range_f32(c, plan, P, npx, st, e) : render_range_f64(c, plan, P, npx, st, e))) return rc;
+        if ((rc = f32 ? render_range_f32(c, plan, *k, P, npx, st, e) : render_range_f64(c, plan, *k, P, npx, st, e)))
+            return rc;
         done += range;
     } while (done < spp && e == hipSuccess);
     return timed_end(c, st, e, "render launch");

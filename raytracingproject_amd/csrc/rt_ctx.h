@@ -15,6 +15,7 @@
 #include "../../include/rt_hip.h"
 #include "rt_devbuf.h"
 #include "rt_device.h"
+#include "rt_launch.h"
 #include "rt_lbvh.h"
 #include "rt_pack.h"
 
@@ -185,10 +186,13 @@ constexpr int F64_KERNEL_DEFAULT = 4, F64_KERNEL_GRID = 5, F64_KERNEL_GRID_FLAT 
 // resident (the smaller of the register and LDS limits, at least 1).  grid_in_reach: every ray
 // the launch can start lies within the sphere grid's reach (grid_reach_ok), so a scene with a
 // grid may walk it; queries that belong to no launch plan one within reach.
+// kernel: the uninstrumented instantiation for (block, wpe, trav) or the f64_kernel; null where
+// none is built -- block / trav / wpe are then the tuning's own key, for the refusal to name.
 struct LaunchPlan {
     int block, trav, wpe, f64_kernel, mesh_stack;
     size_t lds_bytes;
     int wgs_per_cu;
+    const rtx::RenderKernel* kernel;
 };
 LaunchPlan plan_launch(const rt_ctx* c, bool grid_in_reach);
 // rt_plan.cpp: what a job-list query (call: RT_QUERY_PIXELS rt_render_pixels, RT_QUERY_MOMENTS

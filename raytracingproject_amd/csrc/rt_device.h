@@ -15,6 +15,7 @@
 #include "rt_scene.h"
 #include "rt_batch_cull.h"
 #include "rt_quant.h"
+#include "rt_trav.h"
 
 
 namespace rtx {
@@ -682,11 +683,7 @@ __device__ __forceinline__ float cons_tmax(double tmax) { return (float)tmax * (
 //   131072 (with 65536; added by the C ABI where the grid is one cell tall in y, unless 262144
 //      is asked for) the walk steps in x and z only (r06: C3 -6 %, the same frame)
 //   (262144, tuning only, never in a kernel key: keep the 3-D walk on such a grid)
-enum { TRAV_SELROOT = 8, TRAV_B128 = 16, TRAV_F32BOX = 32, TRAV_COH = 64, TRAV_NOSUM = 128, TRAV_TBIN = 256,
-       TRAV_CULL = 512, TRAV_PERSIST = 2048, TRAV_MTOP = 4096, TRAV_MIFIF = 8192, TRAV_MWHILE = 16384,
-       TRAV_MQ = 32768, TRAV_GRID = 65536, TRAV_GFLAT = 131072,
-       TRAV_G3D = 262144 };
-constexpr int TRAV_REMOVED = TRAV_TBIN | TRAV_MTOP;   // refused (r04)
+// (the TRAV_* enum itself: rt_trav.h)
 // FIFO entries per wave (r03: a 64-entry FIFO, where a batch waits until the FIFO is
 // empty, freed 12 KB of LDS per workgroup but ran 3.5 % slower on C3)
 constexpr int coh_fifo_entries(int) { return COH_FIFO; }

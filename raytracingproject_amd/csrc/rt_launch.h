@@ -6,45 +6,67 @@
 #include <cstddef>
 #include <cstdint>
 
+#include "rt_trav.h"
+
 namespace rtx {
 
 struct RenderParams;
 
+// One instantiated frame kernel, render_kernel<...> of rt_render_impl.h.  The kernel units keep
+// one table of these per precision (rt_render_f32.hip, rt_render_f64.hip); every entry's key and
+// kernel come from the same template arguments.
+// block: 256, 448, 512, 768 or 1024 threads (4..16 tiles per workgroup, one scene copy in LDS);
+// mesh: the scene has a triangle mesh (fewer instantiated variants); diag: the instrumented copy
+// (rt_render_diag: loop utilisation counters and timeline stamps into P.diag), built for the
+// kernels that render frames by default.
+struct RenderKernel {
+    int block, wpe, trav;   // the key, as the tuning and the plan name it (wpe 0: the compiler's budget)
+    bool mesh, diag;
+    int f64_kernel;         // rt_tuning.f64_kernel (3..6); 0 for fp32
+    void (*fn)(RenderParams);   // the host handle of render_kernel<...>
+};
+const RenderKernel* find_render_f32(int block, int wpe, int trav, bool mesh, bool diag);   // null: not built
+const RenderKernel* find_render_f64(int kernel, bool mesh);
+// VGPRs per lane (they set how many workgroups share a CU) and static LDS bytes (the sphere
+// grid's walk addresses its dynamic LDS from 0, so a grid kernel must have none); -1, -1 where
+// HIP could not answer.  HIP is asked once per kernel and process; a failed query is not kept.
+struct KernelAttrs { int vgprs, static_lds; };
+KernelAttrs render_kernel_attrs(const RenderKernel* k);
+// k over the work queue of P on persistent lanes: a workgroup per `block / 64` items, at most
+// P.max_wgs; nothing to do is hipSuccess without a launch
+hipError_t launch_render(const RenderKernel& k, const RenderParams& P, size_t lds_bytes, hipStream_t stream);
 
-// block: 256, 448, 512 or 1024 threads (4..16 tiles per workgroup, one scene copy in LDS);
-// mesh: the scene has a triangle mesh (fewer instantiated variants)
-bool render_f32_supported(int block, int waves_per_eu, int trav, bool mesh);
-// VGPRs per lane of an instantiated kernel (-1 if unknown): sets how many workgroups share a CU
-int render_f32_vgprs(int block, int waves_per_eu, int trav, bool mesh);
-int render_f64_vgprs(bool mesh, int kernel);   // kernel: rt_tuning.f64_kernel (3, 4)
-// static LDS bytes of an instantiated render kernel (-1: not instantiated / query failed); the
-// sphere grid's walk addresses its dynamic LDS from 0, so a grid kernel must have none
-int render_f32_static_lds(int block, int waves_per_eu, int trav, bool mesh);
-int render_f32_diag_static_lds(int block, int waves_per_eu, int trav, bool mesh);   // the instrumented copy's
-int render_f64_static_lds(bool mesh, int kernel);
-int render_f64_block(int kernel);              // its threads per workgroup (-1: no such kernel)
-int render_f64_trav(int kernel);               // its traversal flags (TRAV_*)
-hipError_t launch_render_f32(const RenderParams& P, size_t lds_bytes, hipStream_t stream, int block, int waves_per_eu,
-                             int spec);
-// instrumented builds (rt_render_diag): loop utilisation counters and timeline stamps into
-// P.diag, for the (block, waves_per_eu, traversal) combinations that render frames
-bool render_f32_diag_supported(int block, int waves_per_eu, int trav, bool mesh);
-hipError_t launch_render_f32_diag(const RenderParams& P, size_t lds_bytes, hipStream_t stream, int trav, int block,
-                                  int waves_per_eu);
-hipError_t launch_render_f64(const RenderParams& P, size_t lds_bytes, hipStream_t stream, int kernel);
+// The small kernels' launch: one thread per element of [0, n), 256 to a workgroup; nothing to do
+// is hipSuccess without a launch.  The second form bounds the workgroups (max_grid) of a kernel
+// that strides over the elements left, and gives it dynamic LDS.
+template <class Kernel, class N, class... Args>
+inline hipError_t launch_1d_capped(Kernel kernel, N n, N max_grid, size_t lds_bytes, hipStream_t stream,
+                                   const Args&... args) {
+    if (n <= 0) return hipSuccess;
+    const N want = (n + 255) / 256;
+    hipLaunchKernelGGL(kernel, dim3((unsigned)(want < max_grid ? want : max_grid)), dim3(256), lds_bytes, stream,
+                       args...);
+    return hipGetLastError();
+}
+template <class Kernel, class N, class... Args>
+inline hipError_t launch_1d(Kernel kernel, N n, hipStream_t stream, const Args&... args) {
+    return launch_1d_capped(kernel, n, n, 0, stream, args...);
+}
+
 // batched world.hit (rt_trace_rays, rt_trace_rays_from): n rays of 7 values (context precision)
 // -> n rt_hit; origin_ids: null, or per ray the input id of the primitive it starts on, looked
 // up in unmap (n_unmap entries)
-constexpr int TRACE_BLOCK = 256;
-// The traversal flags of the query kernels (TRAV_* by value: this header stands without
-// rt_device.h; rt_radiance.h checks them against the enum): fp32 spheres, fp32 meshes, fp64.  The
-// path kernel of rt_render_pixels (pixels_kernel; fp64: rt_render_pixels_moments' too) adds
+constexpr int TRACE_BLOCK = 256, TRACE_MAX_GRID = 8192;   // (launch_1d_capped: the kernels stride over the rays left)
+// The traversal flags of the query kernels: fp32 spheres (the default frame kernel's select root,
+// whole-record LDS reads and pop culling), fp32 meshes (the if-if mesh loop), fp64 (conservative
+// fp32 slabs).  The path kernel of rt_render_pixels (pixels_kernel; fp64: rt_render_pixels_moments' too) adds
 // QUERY_GRID, or QUERY_GRID | QUERY_GFLAT, where the call's plan walks the sphere grid (rt_ctx.h
 // plan_job_query) -- the `grid` argument of its launchers, 0 for the tree.  A mesh scene has no
 // grid instantiation: grid != 0 there is refused.  The fp32 moments kernel and the first-hit
 // kernels have none either: measured, the grid did not pay there.
-constexpr int QUERY_TRAV_SPHERES = 8 | 16 | 512, QUERY_TRAV_MESH = 8 | 512 | 8192, QUERY_TRAV_F64 = 32;
-constexpr int QUERY_GRID = 65536, QUERY_GFLAT = 131072;
+constexpr int QUERY_TRAV_SPHERES = TRAV_SELROOT | TRAV_B128 | TRAV_CULL,
+              QUERY_TRAV_MESH = TRAV_SELROOT | TRAV_CULL | TRAV_MIFIF, QUERY_TRAV_F64 = TRAV_F32BOX;
+constexpr int QUERY_GRID = TRAV_GRID, QUERY_GFLAT = TRAV_GFLAT;
 hipError_t launch_trace_f32(const RenderParams& P, size_t lds_bytes, hipStream_t stream, const void* rays, int n,
                             void* hits, const int* remap, const int* origin_ids, const int* unmap, int n_unmap,
                             bool diag);
@@ -77,6 +99,7 @@ hipError_t launch_pixel_scan(const void* jobs, int num_jobs, uint32_t npix, unsi
                              size_t* temp_bytes, hipStream_t stream);
 // rt_camera_rays: flat samples [0, total) -> rays (7 values each), keys (rt_path_key), ray_job
 // (may be null); P carries the camera and the seed only
+constexpr long long CAMERA_RAYS_MAX_GRID = 65536;
 hipError_t launch_camera_rays_f32(const RenderParams& P, hipStream_t stream, const void* jobs,
                                   const unsigned long long* offsets, int num_jobs, long long total, void* rays,
                                   void* keys, int32_t* ray_job);

@@ -1,11 +1,8 @@
 // rt_plan.cpp -- the launch plan of a context's scene (rt_ctx.h plan_launch): the occupancy
 // model of the render kernels (registers and LDS per workgroup) and the search over the
 // instantiated candidates.  Pure host arithmetic over the context's scene sizes and tuning,
-// plus the kernels' register counts, which HIP is asked for once each.
+// plus the kernels' register counts (render_kernel_attrs).
 #include <algorithm>
-#include <array>
-#include <map>
-#include <mutex>
 
 #include "rt_ctx.h"
 #include "rt_launch.h"
@@ -34,28 +31,6 @@ size_t lds_scene_bytes_at(const rt_ctx* c, int block, int tr) {
 
 namespace {
 
-// VGPRs of an instantiated render kernel.  The plan weighs every candidate kernel, LDS
-// stack depth and sum / no-sum choice on each call, and a kernel's
-// register count never changes within a process: each is asked of HIP once (failed queries
-// are not kept).
-int kernel_vgprs(bool f64, bool mesh, int block, int wpe, int tr, int f64k) {
-    static std::mutex mu;
-    static std::map<std::array<int, 6>, int> known;
-    const std::array<int, 6> key = f64 ? std::array<int, 6>{1, mesh, 0, 0, 0, f64k}
-                                       : std::array<int, 6>{0, mesh, block, wpe, tr, 0};
-    {
-        std::lock_guard<std::mutex> g(mu);
-        const auto it = known.find(key);
-        if (it != known.end()) return it->second;
-    }
-    const int v = f64 ? render_f64_vgprs(mesh, f64k) : render_f32_vgprs(block, wpe, tr, mesh);
-    if (v > 0) {
-        std::lock_guard<std::mutex> g(mu);
-        known[key] = v;
-    }
-    return v;
-}
-
 // The planner of one launch: the context's scene and tuning, and whether the launch may walk
 // the sphere grid.
 struct Planner {
@@ -74,6 +49,13 @@ struct Planner {
                       : (c->tuning.traversal & TRAV_GRID) ? F64_KERNEL_GRID : F64_KERNEL_DEFAULT;
         if (k != F64_KERNEL_GRID) return k;
         return !grid_usable ? F64_KERNEL_DEFAULT : grid_flat() ? F64_KERNEL_GRID_FLAT : k;
+    }
+
+    // The uninstrumented render kernel at (block, tr, wpe) -- fp64: the f64_kernel -- or null.
+    const RenderKernel* kernel_at(int block, int tr, int wpe) const {
+        const bool mesh = c->scene.n_mnodes > 0;
+        return c->precision == RT_PREC_F64 ? find_render_f64(f64_kernel_of(), mesh)
+                                           : find_render_f32(block, wpe, tr, mesh, false);
     }
 
     // LDS of the sphere part of one workgroup at (block, kernel flags tr): the scene copy and
@@ -110,8 +92,7 @@ struct Planner {
     // register file lets share a CU (LDS aside): 512 VGPRs per SIMD lane, 8-register granules,
     // at most 8 waves per SIMD, 4 SIMDs.
     int wgs_per_cu_bt(int block, int tr, int wpe) const {
-        const bool mesh = c->scene.n_mnodes > 0;
-        const int v = kernel_vgprs(c->precision == RT_PREC_F64, mesh, block, wpe, tr, f64_kernel_of());
+        const int v = render_kernel_attrs(kernel_at(block, tr, wpe)).vgprs;
         int waves = v > 0 ? 512 / ((v + 7) & ~7) : 8;
         if (waves > 8) waves = 8;
         const int wgs = waves * 4 / (block / 64);
@@ -178,8 +159,10 @@ struct Planner {
         // (TRAV_MWHILE, never part of a kernel key) is asked for
         const bool want_mifif = (t & TRAV_MIFIF) || !(t & TRAV_MWHILE);
         t &= ~(TRAV_MWHILE | TRAV_MIFIF | TRAV_GFLAT | TRAV_G3D);
-        if (c->precision == RT_PREC_F64)
-            return {render_f64_block(f64_kernel_of()), render_f64_trav(f64_kernel_of()), 0};
+        if (c->precision == RT_PREC_F64) {
+            const RenderKernel* k = find_render_f64(f64_kernel_of(), false);   // (rt_set_tuning: an instantiated one)
+            return {k ? k->block : -1, k ? k->trav : 0, 0};
+        }
         // the sphere grid wherever the scene has one (build_sphere_grid): the fp32 sphere kernels,
         // the fp32 mixed-scene mesh kernels (74328 / 74456, candidates below) and, through
         // f64_kernel 5, fp64 (handled above); else the tree
@@ -187,7 +170,7 @@ struct Planner {
         // the flat walk (TRAV_GFLAT) wherever the grid is one cell tall in y and its kernel exists
         const bool flat = grid_flat();
         auto gflat = [&](int b, int w, int x, bool mesh) {
-            return flat && (x & TRAV_GRID) && render_f32_supported(b, w, x | TRAV_GFLAT, mesh) ? x | TRAV_GFLAT : x;
+            return flat && (x & TRAV_GRID) && find_render_f32(b, w, x | TRAV_GFLAT, mesh, false) ? x | TRAV_GFLAT : x;
         };
         if (c->scene.n_mnodes == 0) {
             const int b = c->tuning.block, w = c->tuning.waves_per_eu;
@@ -220,17 +203,17 @@ struct Planner {
                 const int t = gi ? t0 & ~TRAV_GRID : t0;
                 // (the if-if loop where its kernel exists, decided before the LDS sums are weighed)
                 auto mifif = [&](int x) {
-                    return want_mifif && render_f32_supported(b, w, x | TRAV_MIFIF, true) ? x | TRAV_MIFIF : x;
+                    return want_mifif && find_render_f32(b, w, x | TRAV_MIFIF, true, false) ? x | TRAV_MIFIF : x;
                 };
                 int tb = mifif(t);
                 if ((t & TRAV_COH) && !(t & TRAV_NOSUM)) {
                     const int tn = mifif(t | TRAV_NOSUM);
-                    const bool ok_with = render_f32_supported(b, w, tb, true);
-                    const bool ok_without = render_f32_supported(b, w, tn, true);
+                    const bool ok_with = find_render_f32(b, w, tb, true, false) != nullptr;
+                    const bool ok_without = find_render_f32(b, w, tn, true, false) != nullptr;
                     // (an uninstantiated kernel has no register count: only instantiated ones compete)
                     if (!ok_with || (ok_without && occupancy_bt(b, tb, w) < occupancy_bt(b, tn, w))) tb = tn;
                 }
-                if (render_f32_supported(b, w, tb, true)) cand[nc++] = {b, gflat(b, w, tb, true), w};
+                if (find_render_f32(b, w, tb, true, false)) cand[nc++] = {b, gflat(b, w, tb, true), w};
             }
         }
         // the if-if loop wherever one of its kernels serves the request: the while-while kernels
@@ -273,6 +256,7 @@ LaunchPlan plan_launch(const rt_ctx* c, bool grid_in_reach) {
     const Planner p{c, c->scene.grid_nodes > 0 && grid_in_reach};
     LaunchPlan r = p.plan_of();
     r.f64_kernel = p.f64_kernel_of();
+    r.kernel = p.kernel_at(r.block, r.trav, r.wpe);
     r.mesh_stack = p.mesh_stack_bt(r.block, r.trav, r.wpe);
     r.lds_bytes = p.lds_sphere_bytes_bt(r.block, r.trav) + p.lds_mesh_bytes_at(r.block, r.trav, r.mesh_stack);
     // persistent lanes: no more workgroups than the device keeps resident

@@ -37,10 +37,6 @@ struct PathKey {   // = rt_path_key (include/rt_hip.h)
     uint32_t pixel, sample, first_draw, pad;
 };
 static_assert(sizeof(PathKey) == 16, "rt_path_key");
-static_assert(QUERY_TRAV_SPHERES == (TRAV_SELROOT | TRAV_B128 | TRAV_CULL) &&
-                  QUERY_TRAV_MESH == (TRAV_SELROOT | TRAV_CULL | TRAV_MIFIF) && QUERY_TRAV_F64 == TRAV_F32BOX &&
-                  QUERY_GRID == TRAV_GRID && QUERY_GFLAT == TRAV_GFLAT,
-              "rt_launch.h names the query kernels' flags by value");
 
 // The persistent loop itself, shared by radiance_kernel, pixels_kernel (rt_pixels.h) and
 // pixels_moments_kernel (rt_moments.h): the scene load, the lane's path state, the claim from the

@@ -11,7 +11,7 @@
 
 namespace rtx {
 
-// The fp64 kernels (rt_tuning.f64_kernel), (id, waves_per_eu, traversal flags, block):
+// The fp64 kernels (rt_tuning.f64_kernel; rt_launch.h RenderKernel):
 //  3 conservative fp32 slab tests (TRAV_F32BOX: each slab widened by a bound of its
 //    rounding, so no box the exact ray enters is rejected) on persistent lanes over the
 //    work queue (TRAV_PERSIST, render_lanes<EXACT>: each sample's radiance stored, ordered
@@ -30,71 +30,26 @@ namespace rtx {
 //    rounding), every listed sphere tested in fp64 -- the same frame bit for bit.
 //  6 (r06; never asked for: the C ABI runs it for 5 where the grid is one cell tall in y,
 //    unless the traversal carries 262144) kernel 5 with the flat walk (TRAV_GFLAT).
-#define RT_F64_VARIANTS(X)                                                                     \
-    X(3, 4, TRAV_F32BOX | TRAV_PERSIST, 512) X(4, 4, TRAV_F32BOX | TRAV_PERSIST | TRAV_COH, 512) \
-    X(5, 4, TRAV_F32BOX | TRAV_PERSIST | TRAV_COH | TRAV_GRID, 512)                               \
-    X(6, 4, TRAV_F32BOX | TRAV_PERSIST | TRAV_COH | TRAV_GRID | TRAV_GFLAT, 512)
-
-int render_f64_block(int kernel) {
-#define RT_F64_BLK(K, W, T, B) \
-    if (kernel == K) return B;
-    RT_F64_VARIANTS(RT_F64_BLK)
-#undef RT_F64_BLK
-    return -1;
+//
+// An entry's key and its kernel come from the same template arguments; each kernel is built for
+// scenes with a mesh and without.
+template <int K, int W, int T, int B, bool MESH>
+constexpr RenderKernel entry() {
+    return {B, W, T, MESH, false, K, render_kernel<double, true, B, W, false, T, MESH>};
 }
+constexpr int LANES = TRAV_F32BOX | TRAV_PERSIST, COH = LANES | TRAV_COH, GRID = COH | TRAV_GRID,
+              GFLAT = GRID | TRAV_GFLAT;
+constexpr RenderKernel F64_KERNELS[] = {
+    entry<3, 4, LANES, 512, true>(), entry<3, 4, LANES, 512, false>(),   //
+    entry<4, 4, COH, 512, true>(),   entry<4, 4, COH, 512, false>(),     //
+    entry<5, 4, GRID, 512, true>(),  entry<5, 4, GRID, 512, false>(),    //
+    entry<6, 4, GFLAT, 512, true>(), entry<6, 4, GFLAT, 512, false>(),
+};
 
-int render_f64_vgprs(bool mesh, int kernel) {
-    hipFuncAttributes a;
-    hipError_t e = hipErrorInvalidValue;
-#define RT_F64_ATTR(K, W, T, B)                                                                            \
-    if (kernel == K)                                                                                       \
-        e = mesh ? hipFuncGetAttributes(&a, (const void*)render_kernel<double, true, B, W, false, T, true>) \
-                 : hipFuncGetAttributes(&a, (const void*)render_kernel<double, true, B, W, false, T, false>);
-    RT_F64_VARIANTS(RT_F64_ATTR)
-#undef RT_F64_ATTR
-    return e == hipSuccess ? a.numRegs : -1;
-}
-
-int render_f64_static_lds(bool mesh, int kernel) {
-    hipFuncAttributes a;
-    hipError_t e = hipErrorInvalidValue;
-#define RT_F64_SLDS(K, W, T, B)                                                                            \
-    if (kernel == K)                                                                                       \
-        e = mesh ? hipFuncGetAttributes(&a, (const void*)render_kernel<double, true, B, W, false, T, true>) \
-                 : hipFuncGetAttributes(&a, (const void*)render_kernel<double, true, B, W, false, T, false>);
-    RT_F64_VARIANTS(RT_F64_SLDS)
-#undef RT_F64_SLDS
-    return e == hipSuccess ? (int)a.sharedSizeBytes : -1;
-}
-
-hipError_t launch_render_f64(const RenderParams& P, size_t lds_bytes, hipStream_t stream, int kernel) {
-#define RT_F64_LAUNCH(K, W, T, B)                                                                          \
-    if (kernel == K) {                                                                                     \
-        constexpr int waves = B / 64;                                                                      \
-        long items = 0; /* persistent lanes: the queue's items, resident workgroups only */                \
-        for (int p = 0; p < P.nph; ++p) items += (long)P.shard_tiles * P.ph_k[p];                          \
-        int grid = (int)((items + waves - 1) / waves);                                                     \
-        if (grid > P.max_wgs) grid = P.max_wgs;                                                            \
-        if (grid == 0) return hipSuccess;                                                                  \
-        if (P.n_mnodes > 0)                                                                                \
-            hipLaunchKernelGGL((render_kernel<double, true, B, W, false, T, true>), dim3(grid), dim3(B),   \
-                               lds_bytes, stream, P);                                                      \
-        else                                                                                               \
-            hipLaunchKernelGGL((render_kernel<double, true, B, W, false, T, false>), dim3(grid), dim3(B),  \
-                               lds_bytes, stream, P);                                                      \
-        return hipGetLastError();                                                                          \
-    }
-    RT_F64_VARIANTS(RT_F64_LAUNCH)
-#undef RT_F64_LAUNCH
-    return hipErrorInvalidValue;
-}
-
-int render_f64_trav(int kernel) {
-#define RT_F64_TRV(K, W, T, B) \
-    if (kernel == K) return (T);
-    RT_F64_VARIANTS(RT_F64_TRV)
-#undef RT_F64_TRV
-    return 0;
+const RenderKernel* find_render_f64(int kernel, bool mesh) {
+    for (const RenderKernel& k : F64_KERNELS)
+        if (k.f64_kernel == kernel && k.mesh == mesh) return &k;
+    return nullptr;
 }
 
 hipError_t launch_tape_f64(const RenderParams& P, int max_depth, const double* ray7, const double* tape, int tape_len,
@@ -124,29 +79,18 @@ hipError_t launch_unshard(const void* gathered, void* frame, int elem_bytes, int
 
 hipError_t launch_reduce(const void* samples, void* out, int elem_bytes, size_t n, int nsamples, int accumulate,
                          hipStream_t stream) {
-    if (n == 0) return hipSuccess;
-    const dim3 block(256), grid((unsigned)((n + 255) / 256));
     if (elem_bytes == 8)
-        hipLaunchKernelGGL(reduce_kernel<double>, grid, block, 0, stream, (const double*)samples, (double*)out, n,
-                           nsamples, accumulate);
-    else if (elem_bytes == 4)
-        hipLaunchKernelGGL(reduce_kernel<float>, grid, block, 0, stream, (const float*)samples, (float*)out, n,
-                           nsamples, accumulate);
-    else
-        return hipErrorInvalidValue;
-    return hipGetLastError();
+        return launch_1d(reduce_kernel<double>, n, stream, (const double*)samples, (double*)out, n, nsamples,
+                         accumulate);
+    if (elem_bytes == 4)
+        return launch_1d(reduce_kernel<float>, n, stream, (const float*)samples, (float*)out, n, nsamples, accumulate);
+    return hipErrorInvalidValue;
 }
 
 hipError_t launch_quantize(const void* frame, int elem_bytes, int32_t* rgb, size_t n, int spp, hipStream_t stream) {
-    if (n == 0) return hipSuccess;
-    const dim3 block(256), grid((unsigned)((n + 255) / 256));
-    if (elem_bytes == 8)
-        hipLaunchKernelGGL(quantize_kernel<double>, grid, block, 0, stream, (const double*)frame, rgb, n, spp);
-    else if (elem_bytes == 4)
-        hipLaunchKernelGGL(quantize_kernel<float>, grid, block, 0, stream, (const float*)frame, rgb, n, spp);
-    else
-        return hipErrorInvalidValue;
-    return hipGetLastError();
+    if (elem_bytes == 8) return launch_1d(quantize_kernel<double>, n, stream, (const double*)frame, rgb, n, spp);
+    if (elem_bytes == 4) return launch_1d(quantize_kernel<float>, n, stream, (const float*)frame, rgb, n, spp);
+    return hipErrorInvalidValue;
 }
 
 hipError_t launch_finish_u8(const void* gathered, int elem_bytes, uint8_t* rgb, int W, int H, int tiles_x,
@@ -235,37 +179,23 @@ __global__ void reconcile_accum_kernel(const float* __restrict__ out, long long*
 // Batched world.hit (rt_trace_rays), fp64: the reference's arithmetic (sphere.h:30-57).
 hipError_t launch_trace_f64(const RenderParams& P, size_t lds_bytes, hipStream_t stream, const void* rays, int n,
                             void* hits, const int* remap, const int* origin_ids, const int* unmap, int n_unmap) {
-    if (n <= 0) return hipSuccess;
-    constexpr int B = TRACE_BLOCK;
-    const int grid = (n + B - 1) / B < 8192 ? (n + B - 1) / B : 8192;
-    const double* r = (const double*)rays;
-    TraceHit* h = (TraceHit*)hits;
     // the default fp64 kernel's box tests (conservative fp32 slabs)
-    if (P.n_mnodes > 0)
-        hipLaunchKernelGGL((trace_kernel<double, true, B, TRAV_F32BOX, true>), dim3(grid), dim3(B), lds_bytes, stream,
-                           P, r, n, h, remap, origin_ids, unmap, n_unmap);
-    else
-        hipLaunchKernelGGL((trace_kernel<double, true, B, TRAV_F32BOX, false>), dim3(grid), dim3(B), lds_bytes, stream,
-                           P, r, n, h, remap, origin_ids, unmap, n_unmap);
-    return hipGetLastError();
+    constexpr int B = TRACE_BLOCK, T = QUERY_TRAV_F64;
+    const auto kernel =
+        P.n_mnodes > 0 ? trace_kernel<double, true, B, T, true> : trace_kernel<double, true, B, T, false>;
+    return launch_1d_capped(kernel, n, TRACE_MAX_GRID, lds_bytes, stream, P, (const double*)rays, n, (TraceHit*)hits,
+                            remap, origin_ids, unmap, n_unmap);
 }
 
 // Batched any-hit visibility (rt_occluded), fp64: the reference's boolean (hittable.h:28) --
 // spheres and triangles in its fp64 arithmetic, conservative fp32 boxes that only prune.
 hipError_t launch_occluded_f64(const RenderParams& P, size_t lds_bytes, hipStream_t stream, const void* rays, int n,
                                const void* intervals, uint8_t* occluded) {
-    if (n <= 0) return hipSuccess;
-    constexpr int B = TRACE_BLOCK;
-    const int grid = (n + B - 1) / B < 8192 ? (n + B - 1) / B : 8192;
-    const double* r = (const double*)rays;
-    const double* iv = (const double*)intervals;
-    if (P.n_mnodes > 0)
-        hipLaunchKernelGGL((occluded_kernel<double, true, B, TRAV_F32BOX, true>), dim3(grid), dim3(B), lds_bytes,
-                           stream, P, r, n, iv, occluded);
-    else
-        hipLaunchKernelGGL((occluded_kernel<double, true, B, TRAV_F32BOX, false>), dim3(grid), dim3(B), lds_bytes,
-                           stream, P, r, n, iv, occluded);
-    return hipGetLastError();
+    constexpr int B = TRACE_BLOCK, T = QUERY_TRAV_F64;
+    const auto kernel =
+        P.n_mnodes > 0 ? occluded_kernel<double, true, B, T, true> : occluded_kernel<double, true, B, T, false>;
+    return launch_1d_capped(kernel, n, TRACE_MAX_GRID, lds_bytes, stream, P, (const double*)rays, n,
+                            (const double*)intervals, occluded);
 }
 
 // Batched ray_color (rt_radiance_rays), fp64: the reference's arithmetic with the default fp64
@@ -275,26 +205,19 @@ hipError_t launch_radiance_f64(const RenderParams& P, size_t lds_bytes, hipStrea
                                const void* keys, void* radiance, uint32_t* segments, int n_cu) {
     if (n <= 0) return hipSuccess;
     constexpr int B = TRACE_BLOCK;
-    return launch_for_scene<radiance_kernel<double, true, B, 4, TRAV_F32BOX, true>,
-                            radiance_kernel<double, true, B, 4, TRAV_F32BOX, false>, B>(
+    return launch_for_scene<radiance_kernel<double, true, B, 4, QUERY_TRAV_F64, true>,
+                            radiance_kernel<double, true, B, 4, QUERY_TRAV_F64, false>, B>(
         P, lds_bytes, stream, n, n_cu, 0, (const double*)rays, n, (const PathKey*)keys, (double*)radiance, segments);
 }
 
 hipError_t launch_reconcile_accum(const float* out, long long* accum, uint32_t* flags, size_t npx,
                                   hipStream_t stream) {
-    if (npx == 0) return hipSuccess;
-    hipLaunchKernelGGL(reconcile_accum_kernel, dim3((unsigned)((npx + 255) / 256)), dim3(256), 0, stream, out, accum,
-                       flags, npx);
-    return hipGetLastError();
+    return launch_1d(reconcile_accum_kernel, npx, stream, out, accum, flags, npx);
 }
 
 hipError_t launch_finalize(long long* accum, const unsigned long long* packed, const uint32_t* flags, float* out,
                            size_t npx, hipStream_t stream) {
-    const size_t n = npx * 3;
-    if (n == 0) return hipSuccess;
-    hipLaunchKernelGGL(finalize_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, accum, packed, flags,
-                       out, n);
-    return hipGetLastError();
+    return launch_1d(finalize_kernel, npx * 3, stream, accum, packed, flags, out, npx * 3);
 }
 
 // ---- sparse rendering (rt_render_pixels, rt_camera_rays; rt_pixels.h) -----------------------
@@ -309,11 +232,8 @@ hipError_t launch_pixel_scan(const void* jobs, int num_jobs, uint32_t npix, unsi
 hipError_t launch_camera_rays_f64(const RenderParams& P, hipStream_t stream, const void* jobs,
                                   const unsigned long long* offsets, int num_jobs, long long total, void* rays,
                                   void* keys, int32_t* ray_job) {
-    if (total <= 0) return hipSuccess;
-    const int grid = (int)((total + 255) / 256 < 65536 ? (total + 255) / 256 : 65536);
-    hipLaunchKernelGGL(camera_rays_kernel<double>, dim3(grid), dim3(256), 0, stream, P, (const PixelJob*)jobs, offsets,
-                       num_jobs, total, (double*)rays, (PathKey*)keys, ray_job);
-    return hipGetLastError();
+    return launch_1d_capped(camera_rays_kernel<double>, total, CAMERA_RAYS_MAX_GRID, 0, stream, P,
+                            (const PixelJob*)jobs, offsets, num_jobs, total, (double*)rays, (PathKey*)keys, ray_job);
 }
 
 // Sparse rendering (rt_render_pixels), fp64: launch_radiance_f64's box tests, register budget
@@ -343,11 +263,8 @@ hipError_t launch_pixels_f64(const RenderParams& P, size_t lds_bytes, hipStream_
 hipError_t launch_pixels_reduce(const unsigned long long* offsets, int num_jobs, unsigned long long q_begin,
                                 unsigned long long q_end, const double* samples, const uint32_t* sample_segs,
                                 int accumulate, double* out_sums, uint32_t* out_segments, hipStream_t stream) {
-    if (num_jobs <= 0) return hipSuccess;
-    hipLaunchKernelGGL((pixels_reduce_kernel<double, false>), dim3((unsigned)((num_jobs + 255) / 256)), dim3(256), 0,
-                       stream, offsets, num_jobs, q_begin, q_end, samples, sample_segs, accumulate, out_sums,
-                       (double*)nullptr, out_segments);
-    return hipGetLastError();
+    return launch_1d(pixels_reduce_kernel<double, false>, num_jobs, stream, offsets, num_jobs, q_begin, q_end, samples,
+                     sample_segs, accumulate, out_sums, (double*)nullptr, out_segments);
 }
 
 // fp32, one thread per job, before the path kernel: the job's fixed-point sums start at 0, or
@@ -387,18 +304,13 @@ __global__ void px_finalize_kernel(const unsigned long long* __restrict__ offset
 
 hipError_t launch_pixels_seed(const unsigned long long* offsets, int num_jobs, int accumulate, const float* out_sums,
                               long long* acc, uint32_t* flags, uint32_t* out_segments, hipStream_t stream) {
-    if (num_jobs <= 0) return hipSuccess;
-    hipLaunchKernelGGL(px_seed_kernel, dim3((unsigned)((num_jobs + 255) / 256)), dim3(256), 0, stream, offsets,
-                       num_jobs, accumulate, out_sums, acc, flags, out_segments);
-    return hipGetLastError();
+    return launch_1d(px_seed_kernel, num_jobs, stream, offsets, num_jobs, accumulate, out_sums, acc, flags,
+                     out_segments);
 }
 
 hipError_t launch_pixels_finalize(const unsigned long long* offsets, int num_jobs, int accumulate,
                                   const long long* acc, const uint32_t* flags, float* out_sums, hipStream_t stream) {
-    if (num_jobs <= 0) return hipSuccess;
-    hipLaunchKernelGGL(px_finalize_kernel, dim3((unsigned)((num_jobs + 255) / 256)), dim3(256), 0, stream, offsets,
-                       num_jobs, accumulate, acc, flags, out_sums);
-    return hipGetLastError();
+    return launch_1d(px_finalize_kernel, num_jobs, stream, offsets, num_jobs, accumulate, acc, flags, out_sums);
 }
 
 // First-hit auxiliary outputs (rt_render_pixels_aov), fp64: launch_trace_f64's box tests, so a
@@ -419,11 +331,8 @@ hipError_t launch_aov_reduce(const unsigned long long* offsets, int num_jobs, un
                              unsigned long long q_end, const double* records, const int32_t* record_ids,
                              int accumulate, void* carry, double* albedo, double* normal, double* depth, int32_t* id,
                              uint32_t* hits, hipStream_t stream) {
-    if (num_jobs <= 0) return hipSuccess;
-    hipLaunchKernelGGL(aov_reduce_kernel<double>, dim3((unsigned)((num_jobs + 255) / 256)), dim3(256), 0, stream,
-                       offsets, num_jobs, q_begin, q_end, records, record_ids, accumulate, (AovNear*)carry, albedo,
-                       normal, depth, id, hits);
-    return hipGetLastError();
+    return launch_1d(aov_reduce_kernel<double>, num_jobs, stream, offsets, num_jobs, q_begin, q_end, records,
+                     record_ids, accumulate, (AovNear*)carry, albedo, normal, depth, id, hits);
 }
 
 // ---- second moments and refinement (rt_render_pixels_moments, rt_refine_jobs; rt_moments.h) ----
@@ -431,11 +340,8 @@ hipError_t launch_pixels_reduce_moments(const unsigned long long* offsets, int n
                                         unsigned long long q_end, const double* samples, const uint32_t* sample_segs,
                                         int accumulate, double* out_sums, double* out_sumsq, uint32_t* out_segments,
                                         hipStream_t stream) {
-    if (num_jobs <= 0) return hipSuccess;
-    hipLaunchKernelGGL((pixels_reduce_kernel<double, true>), dim3((unsigned)((num_jobs + 255) / 256)), dim3(256), 0,
-                       stream, offsets, num_jobs, q_begin, q_end, samples, sample_segs, accumulate, out_sums, out_sumsq,
-                       out_segments);
-    return hipGetLastError();
+    return launch_1d(pixels_reduce_kernel<double, true>, num_jobs, stream, offsets, num_jobs, q_begin, q_end, samples,
+                     sample_segs, accumulate, out_sums, out_sumsq, out_segments);
 }
 
 // fp32, one thread per job, before the path kernel: the second moment's two words start at 0,
@@ -494,41 +400,29 @@ __global__ void px_finalize_moments_kernel(const unsigned long long* __restrict_
 hipError_t launch_pixels_seed_moments(const unsigned long long* offsets, int num_jobs, int accumulate,
                                       const float* out_sumsq, unsigned long long* sq, uint32_t* sqflags,
                                       hipStream_t stream) {
-    if (num_jobs <= 0) return hipSuccess;
-    hipLaunchKernelGGL(px_seed_moments_kernel, dim3((unsigned)((num_jobs + 255) / 256)), dim3(256), 0, stream, offsets,
-                       num_jobs, accumulate, out_sumsq, sq, sqflags);
-    return hipGetLastError();
+    return launch_1d(px_seed_moments_kernel, num_jobs, stream, offsets, num_jobs, accumulate, out_sumsq, sq, sqflags);
 }
 
 hipError_t launch_pixels_finalize_moments(const unsigned long long* offsets, int num_jobs, int accumulate,
                                           const unsigned long long* sq, const uint32_t* sqflags, float* out_sumsq,
                                           hipStream_t stream) {
-    if (num_jobs <= 0) return hipSuccess;
-    hipLaunchKernelGGL(px_finalize_moments_kernel, dim3((unsigned)((num_jobs + 255) / 256)), dim3(256), 0, stream,
-                       offsets, num_jobs, accumulate, sq, sqflags, out_sumsq);
-    return hipGetLastError();
+    return launch_1d(px_finalize_moments_kernel, num_jobs, stream, offsets, num_jobs, accumulate, sq, sqflags,
+                     out_sumsq);
 }
 
 hipError_t launch_refine_jobs(void* jobs, int num_jobs, const void* sums, const void* sumsq, int elem_bytes,
                               double rel_error, double abs_floor, uint32_t min_samples, uint32_t max_samples,
                               uint32_t max_step, unsigned long long* stats, hipStream_t stream) {
-    if (num_jobs <= 0) return hipSuccess;
     const AdaptiveParams A{rel_error, abs_floor, min_samples, max_samples, max_step, 0u};
-    const dim3 grid((unsigned)((num_jobs + 255) / 256)), block(256);
     if (elem_bytes == 8)
-        hipLaunchKernelGGL(refine_jobs_kernel<double>, grid, block, 0, stream, (PixelJob*)jobs, num_jobs,
-                           (const double*)sums, (const double*)sumsq, A, stats);
-    else
-        hipLaunchKernelGGL(refine_jobs_kernel<float>, grid, block, 0, stream, (PixelJob*)jobs, num_jobs,
-                           (const float*)sums, (const float*)sumsq, A, stats);
-    return hipGetLastError();
+        return launch_1d(refine_jobs_kernel<double>, num_jobs, stream, (PixelJob*)jobs, num_jobs, (const double*)sums,
+                         (const double*)sumsq, A, stats);
+    return launch_1d(refine_jobs_kernel<float>, num_jobs, stream, (PixelJob*)jobs, num_jobs, (const float*)sums,
+                     (const float*)sumsq, A, stats);
 }
 
 hipError_t launch_seed_accum(const float* out, long long* accum, uint32_t* flags, size_t npx, hipStream_t stream) {
-    if (npx == 0) return hipSuccess;
-    hipLaunchKernelGGL(seed_accum_kernel, dim3((unsigned)((npx + 255) / 256)), dim3(256), 0, stream, out, accum,
-                       flags, npx);
-    return hipGetLastError();
+    return launch_1d(seed_accum_kernel, npx, stream, out, accum, flags, npx);
 }
 
 }  // namespace rtx
